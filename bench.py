@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: BinaryMF-Penalty multiplicative-update iterations/s on a 100 000 x 20 000 Boolean X, k = 64.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,13 @@ One "step" is one full iteration of PyBMF's loop body (models/BinaryMFPenalty.py
 Boolean cover counts, regulariser growth and the device-side early-stop test.  X lives in HBM as bits before the
 timed region starts.  N > 1 row-shards X (strong scaling: the problem is fixed) with one exchange per step.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+A plain run sets up, pre-heats and warms up, times exactly K steps and prints ONE JSON line (rank 0) with the driver's
+contract (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` writes what the
+timed loop computed by the end of its last step -- the fp64 factors `U.npy`, `V.npy` and the log table `log.npy` (iteration,
+error, rec_error, reg, reg_error, RMSE, [MAE with --mae 1,] TP, FP, FN, TN per row) -- at most 64 MB in all (a fixed, seeded row sample of a
+larger factor, its row indices in `<name>_rows.npy`).  The inputs are seeded: the same arguments give the same inputs.
+
+`--full` adds everything else the line used to carry, measured after the timed region:
   `roofline`      dominant kernel = the bits GEMM, timed with HIP events on its own stream inside the timed region; `traffic` =
                   fabric-side bytes per launch from rocprofv3 PMC passes of THIS build, made by a child process after the timed
                   region (separate --pmc runs, FETCH_SIZE x 2 + WRITE_SIZE as MI355X_MICROARCH.md prescribes);
@@ -19,7 +25,8 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
   `checks`        the GPU against itself (trace-form vs direct residual) AND against the fp64 oracle: one more update from the
                   final state re-computed exactly on a row / column sample (`oracle_step_rel_U/V`);
   `secondary`     the other BASELINE.json configurations, driver-timed: C1 fit() ms, C2 WNMF it/s, C5 line-search it/s;
-  `repeat`        three more timed legs of K steps (outside `value`) so that the rate can be corroborated.
+  `repeat`        three more timed legs of K steps (outside `value`) so that the rate can be corroborated;
+  `cold_start`, `sustained`, `alt`, `with_mae`, `updates_only` and, for N > 1, the timed exchange and the unsharded floor.
 """
 import argparse
 import contextlib
@@ -546,6 +553,26 @@ def stdout_to_stderr():
         os.close(saved)
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write each (name, 2-D float64 array) as DIR/<name>.npy.  When they would exceed `limit` bytes in all, every array larger
+    than 1 MB keeps a fixed, seeded sample of its rows (sorted), and the row indices go to DIR/<name>_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for _, a in arrays)
+    big = sum(a.nbytes for _, a in arrays if a.nbytes > 10 ** 6)
+    big_idx = sum(a.nbytes + 8 * a.shape[0] for _, a in arrays if a.nbytes > 10 ** 6)   # (+ the row indices of a sample)
+    scale = 1.0 if total <= limit else max(0.0, (0.98 * limit - (total - big)) / big_idx)
+    for j, (name, a) in enumerate(arrays):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if scale < 1.0 and a.nbytes > 10 ** 6:
+            rows = np.sort(np.random.RandomState(seed + j).choice(a.shape[0], size=int(a.shape[0] * scale), replace=False))
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -565,11 +592,17 @@ def main():
     ap.add_argument("--preheat", type=int, default=150,
                     help="untimed iterations of the same loop before the run proper: a fresh process reaches its steady rate only after ~60 ms of GPU "
                          "work (power state / clocks; measured: the SAME 20 iterations of the trajectory run 7 %% faster when 80 iterations went before). "
-                         "The factors are reloaded afterwards; the first K of these iterations are timed too and reported as `cold_start`. 0: off")
+                         "The factors are reloaded afterwards; with --full the first K of these iterations are timed too and reported as `cold_start`. 0: off")
     ap.add_argument("--sustained", type=int, default=5000,
                     help="iterations of the `sustained` leg (outside `value`): the same loop with the stopping rule disabled, long enough (>= 3 s of GPU "
                          "time) for an external sampler to see the GPU busy; 0: off")
-    ap.add_argument("--repeat", type=int, default=-1, help="extra timed legs of K steps after the timed region (default: 3 with --secondary 1, else 0)")
+    ap.add_argument("--repeat", type=int, default=-1, help="extra timed legs of K steps after the timed region (--full only; default: 3 with --secondary 1, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (roofline and traffic, checks against the oracle, CPU baseline, "
+                         "secondary configurations, other operand formats, cold start, repeat and sustained legs); --secondary, --cpu-rows, "
+                         "--traffic, --alt-operands, --sustained and --repeat act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the factors and the log table of the timed loop after its last step as DIR/<name>.npy (float64, <= 64 MB)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--i8-variant", type=int, default=0,
                     help="kernel variant of the whole-factor int8 bits GEMM (bmf_xf_bits_i8_variant; A/B runs: 0 = the default, 4 = the "
@@ -617,8 +650,9 @@ def main():
 
     m, n, k = args.m, args.n, args.k
     K, W = args.steps, args.warmup
-    extra_legs = 0 if (args.pmc_child or not args.secondary) else 3
-    if args.repeat >= 0 and not args.pmc_child:
+    full = args.full and not args.pmc_child
+    extra_legs = 0 if (not full or not args.secondary) else 3
+    if args.repeat >= 0 and full:
         extra_legs = args.repeat
     # planted factors, density 0.067, noise [0.05, 0.01]
     dens = 0.067 if k >= 32 else 0.2
@@ -627,10 +661,10 @@ def main():
     X = BitMatrix(gen, device, row_lo=lo, row_hi=hi)
     del gen
     reg0, growth, max_reg = 1.0, 1.02, 1e10
-    comm_leg = 1 if (sharded and not args.pmc_child) else 0   # one more leg of K steps with the exchange timed by events (outside `value`)
+    comm_leg = 1 if (sharded and full) else 0   # one more leg of K steps with the exchange timed by events (outside `value`)
     n_iter_total = W + K * (1 + extra_legs + comm_leg) + 1    # + the oracle-checked extra update
     preheat = 0 if args.pmc_child else max(0, args.preheat)
-    if preheat:
+    if preheat and full:   # (the pre-heating run holds the timed `cold_start` leg of W + K steps)
         preheat = max(preheat, W + K)
     max_iter = max(n_iter_total, preheat) + 1
     tol = float(os.environ.get("BMF_BENCH_TOL", "0.01"))
@@ -665,22 +699,29 @@ def main():
     cold = None
     if preheat:   # untimed for `value`; its own first K steps after W are what a cold process delivers
         eng.prepare(regs[0])
-        eng.run(regs[:W], it0=1)
-        cold = timed_leg(W, K, 1 + W)
-        eng.run(regs[W + K:preheat], it0=1 + W + K)
+        if full:
+            eng.run(regs[:W], it0=1)
+            cold = timed_leg(W, K, 1 + W)
+            eng.run(regs[W + K:preheat], it0=1 + W + K)
+        else:
+            eng.run(regs[:preheat], it0=1)
         barrier()
         eng.load_factors(U0d, V0d)         # fresh start, device-side (no PCIe wait in which the clocks fall back): log, stop flag and counters are reset too
     eng.prepare(regs[0])
     eng.run(regs[:W], it0=1)
     barrier()
-    L.check(L.lib.bmf_timer_enable(2 * K + 8))
-    L.check(L.lib.bmf_timer_stride(3))   # sample 1 launch in 3 (alternates between X V and X^T U): event pairs cost stream time
+    gemm_timer = full or args.pmc_child  # the roofline's per-launch GEMM time (--full only: event pairs cost stream time)
+    if gemm_timer:
+        L.check(L.lib.bmf_timer_enable(2 * K + 8))
+        L.check(L.lib.bmf_timer_stride(3))   # sample 1 launch in 3 (alternates between X V and X^T U)
     dt = timed_leg(W, K, 1 + W)          # THE timed region: exactly K steps
     n_launch, gemm_ms = C.c_int(0), C.c_double(0.0)
-    L.check(L.lib.bmf_timer_read(C.byref(n_launch), C.byref(gemm_ms)))
-    L.check(L.lib.bmf_timer_disable())
+    if gemm_timer:
+        L.check(L.lib.bmf_timer_read(C.byref(n_launch), C.byref(gemm_ms)))
+        L.check(L.lib.bmf_timer_disable())
     if args.pmc_child:
         return
+    timed_factors = eng.factors() if (args.dump_outputs and rank == 0) else None   # the state after the last timed step
     repeat = [timed_leg(W + K * (1 + j), K, 1 + W + K * (1 + j)) for j in range(extra_legs)]
     done = W + K * (1 + extra_legs)
     comm = None
@@ -712,37 +753,42 @@ def main():
         assert log.shape[0] == 1 + done and stop == 0, (log.shape, stop)
         assert np.isfinite(log[:, :6]).all()
     last = log[W + K]    # the log row at the end of the timed region
+    if timed_factors is not None:
+        cols = [c for c in range(L.LOG_TN + 1) if c != L.LOG_MAE or args.mae]   # (MAE is NaN unless its pass runs)
+        dump_outputs(args.dump_outputs, [("log", log[: W + K + 1, cols]), ("V", timed_factors[1]), ("U", timed_factors[0])])
+        del timed_factors
 
     # checks: (a) the logged trace-form rec_error against a direct residual pass on the GPU and NumPy fp64 on rank 0's first rows;
     # (b) against the ORACLE: one more update from the final state, exact on a row / column sample
     chk = {}
-    sums = torch.zeros(4, dtype=torch.float64, device=device)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(L.lib.bmf_residual_sums(L.ptr(X.bits), X.m_pad, X.ldx, X.m, X.n, L.ptr(eng.U), L.ptr(eng.V), eng.kp, L.ptr(sums), None, stream))
-    if sharded:
-        dist.all_reduce(sums)
-    direct = 0.5 * float(sums[1].item())
-    chk["rec_error_trace_vs_direct_rel"] = abs(direct - log[-1, L.LOG_REC]) / direct
-    if rank == 0:
-        rs = min(1024, X.m)
-        Uh, Vh = eng.factors()
-        Xs = X.rows_dense_u8(0, rs).astype(np.float64)
-        with few_blas_threads():
-            host = float(((Xs - Uh[:rs] @ Vh.T) ** 2).sum())
-        sums.zero_()
-        L.check(L.lib.bmf_residual_sums(L.ptr(X.bits), X.m_pad, X.ldx, rs, X.n, L.ptr(eng.U), L.ptr(eng.V), eng.kp, L.ptr(sums), None, stream))
-        chk["residual_gpu_vs_numpy_fp64_rel"] = abs(float(sums[1].item()) - host) / host
-    if not sharded:
-        rv, ru = oracle_step_check(X, eng, regs[done], 1 + done)
-        chk["oracle_step_rel_V"], chk["oracle_step_rel_U"] = rv, ru
-        chk["oracle_step"] = (f"update {1 + done} from the GPU's own state re-computed by the fp64 oracle on 256 columns (V) and 1024 rows (U) "
-                              "of the full problem; gate 1e-4 (PyBMF/models/BinaryMFPenalty.py:136-163)")
-        if os.environ.get("BMF_NO_CHECK") != "1":
-            assert rv <= 1e-4 and ru <= 1e-4, (rv, ru)
+    if full:
+        sums = torch.zeros(4, dtype=torch.float64, device=device)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        L.check(L.lib.bmf_residual_sums(L.ptr(X.bits), X.m_pad, X.ldx, X.m, X.n, L.ptr(eng.U), L.ptr(eng.V), eng.kp, L.ptr(sums), None, stream))
+        if sharded:
+            dist.all_reduce(sums)
+        direct = 0.5 * float(sums[1].item())
+        chk["rec_error_trace_vs_direct_rel"] = abs(direct - log[-1, L.LOG_REC]) / direct
+        if rank == 0:
+            rs = min(1024, X.m)
+            Uh, Vh = eng.factors()
+            Xs = X.rows_dense_u8(0, rs).astype(np.float64)
+            with few_blas_threads():
+                host = float(((Xs - Uh[:rs] @ Vh.T) ** 2).sum())
+            sums.zero_()
+            L.check(L.lib.bmf_residual_sums(L.ptr(X.bits), X.m_pad, X.ldx, rs, X.n, L.ptr(eng.U), L.ptr(eng.V), eng.kp, L.ptr(sums), None, stream))
+            chk["residual_gpu_vs_numpy_fp64_rel"] = abs(float(sums[1].item()) - host) / host
+        if not sharded:
+            rv, ru = oracle_step_check(X, eng, regs[done], 1 + done)
+            chk["oracle_step_rel_V"], chk["oracle_step_rel_U"] = rv, ru
+            chk["oracle_step"] = (f"update {1 + done} from the GPU's own state re-computed by the fp64 oracle on 256 columns (V) and 1024 rows (U) "
+                                  "of the full problem; gate 1e-4 (PyBMF/models/BinaryMFPenalty.py:136-163)")
+            if os.environ.get("BMF_NO_CHECK") != "1":
+                assert rv <= 1e-4 and ru <= 1e-4, (rv, ru)
 
     # sustained leg (all ranks): the same loop, stopping rule disabled, long enough for an external sampler to see the GPU busy
     sus = None
-    if args.sustained > 0:
+    if full and args.sustained > 0:
         n_s = int(args.sustained)
         regs_s, r = [], np.float64(reg0)
         for _ in range(n_s + 1):
@@ -786,20 +832,6 @@ def main():
         return
 
     its = K / dt
-    launches = max(n_launch.value, 1)
-    avg_ms = gemm_ms.value / launches
-    # algorithmic flops of one bits-GEMM launch on this rank: 2 * m_local * n * k (X V and X^T U are the same count)
-    flops_launch = 2.0 * X.m * n * k
-    achieved = flops_launch / (avg_ms * 1e-3) / 1e12
-    limb_bytes = 1.0 if args.panel == "i8" else 2.0
-    bytes_launch = X.m * n / 8.0 + 0.5 * (X.m + n) * k * (limb_bytes * args.terms + 4.0)
-    peak = MFMA_PEAK_TFLOPS[args.panel]
-    traffic, traffic_note = (None, "skipped")
-    profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCPROFILER")) for k in os.environ)
-    if args.traffic and world == 1 and not sharded and profiled:
-        traffic_note = "skipped: this run is itself under a profiler (no profiler children inside a profiled process)"
-    elif args.traffic and world == 1 and not sharded:
-        traffic, traffic_note = measure_traffic(args)
     out = {
         "metric": "MU iterations/sec (BinaryMF-Penalty, 100k x 20k Boolean, k=64)" if (m, n, k) == (100_000, 20_000, 64)
                   else f"MU iterations/sec (BinaryMF-Penalty, {m}x{n} Boolean, k={k})",
@@ -813,25 +845,40 @@ def main():
                    "mae_pass": bool(args.mae), "operands": args.operands, "row_sharding": f"{world} x {X.m} rows",
                    "splits_xv": eng.splits_xv, "splits_xtu": eng.splits_xtu,
                    "k_limit": "the tuned path takes k <= 64 (one 64-bit word of factor bits per row); 64 < k <= 128 runs BinaryMFPenalty / WNMF on a two-block engine (pybmf_amd/wide.py, Python-driven), larger k raises NotImplementedError"},
-        "roofline": {"kernel": "xf_bits_i8_kernel (X V and X^T U)" if args.panel == "i8" else "xf_bits_kernel (X V and X^T U)",
-                     "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                     "peak_note": f"dense {args.panel} MFMA peak of MI355X_MICROARCH.md (i8 = 2 x the bf16 rate per clock); the kernel issues "
-                                  f"{args.terms} MFMA passes per algorithmic flop (hw_flops_factor)",
-                     "traffic": traffic, "traffic_source": traffic_note, "launches_timed": launches, "avg_launch_ms": avg_ms,
-                     "algorithmic_flops_per_launch": flops_launch, "hw_flops_factor": args.terms,
-                     "frac_of_f16_mfma_peak": achieved / MFMA_PEAK_TFLOPS["f16"],
-                     "mfma_pipe_busy_estimate": args.terms * achieved / peak,
-                     "frac_of_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
-                     # the other roofline of SURVEY 8d: algorithmic bytes of one launch (X as bits once, the factor panel, the
-                     # fp32 result; mean of the X V and X^T U launches) against HBM
-                     "algorithmic_bytes_per_launch": bytes_launch, "frac_of_hbm_peak": bytes_launch / (avg_ms * 1e-3) / HBM_PEAK_BYTES,
-                     "traffic_over_algorithmic": (traffic / bytes_launch) if traffic else None,
-                     "gemm_share_of_step": 2.0 * avg_ms * 1e-3 * K / dt},
         "iteration_vs_fp32_mfma_roofline": its / (FP32_MFMA_PEAK_TFLOPS * 1e12 * world / (4.0 * m * n * k + 4.0 * (m + n) * k * k)),
         "final": {"iter": int(last[L.LOG_ITER]), "error": last[L.LOG_ERROR], "rec_error": last[L.LOG_REC],
                   "reg_error": last[L.LOG_REGERR], "TP": int(last[L.LOG_TP]), "FP": int(last[L.LOG_FP])},
-        "checks": chk,
     }
+    if full:
+        launches = max(n_launch.value, 1)
+        avg_ms = gemm_ms.value / launches
+        # algorithmic flops of one bits-GEMM launch on this rank: 2 * m_local * n * k (X V and X^T U are the same count)
+        flops_launch = 2.0 * X.m * n * k
+        achieved = flops_launch / (avg_ms * 1e-3) / 1e12
+        limb_bytes = 1.0 if args.panel == "i8" else 2.0
+        bytes_launch = X.m * n / 8.0 + 0.5 * (X.m + n) * k * (limb_bytes * args.terms + 4.0)
+        peak = MFMA_PEAK_TFLOPS[args.panel]
+        traffic, traffic_note = (None, "skipped")
+        profiled = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(k.startswith(("ROCPROF", "ROCPROFILER")) for k in os.environ)
+        if args.traffic and world == 1 and not sharded and profiled:
+            traffic_note = "skipped: this run is itself under a profiler (no profiler children inside a profiled process)"
+        elif args.traffic and world == 1 and not sharded:
+            traffic, traffic_note = measure_traffic(args)
+        out["roofline"] = {"kernel": "xf_bits_i8_kernel (X V and X^T U)" if args.panel == "i8" else "xf_bits_kernel (X V and X^T U)",
+                           "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                           "peak_note": f"dense {args.panel} MFMA peak of MI355X_MICROARCH.md (i8 = 2 x the bf16 rate per clock); the kernel issues "
+                                        f"{args.terms} MFMA passes per algorithmic flop (hw_flops_factor)",
+                           "traffic": traffic, "traffic_source": traffic_note, "launches_timed": launches, "avg_launch_ms": avg_ms,
+                           "algorithmic_flops_per_launch": flops_launch, "hw_flops_factor": args.terms,
+                           "frac_of_f16_mfma_peak": achieved / MFMA_PEAK_TFLOPS["f16"],
+                           "mfma_pipe_busy_estimate": args.terms * achieved / peak,
+                           "frac_of_fp32_mfma_peak": achieved / FP32_MFMA_PEAK_TFLOPS,
+                           # the other roofline of SURVEY 8d: algorithmic bytes of one launch (X as bits once, the factor panel, the
+                           # fp32 result; mean of the X V and X^T U launches) against HBM
+                           "algorithmic_bytes_per_launch": bytes_launch, "frac_of_hbm_peak": bytes_launch / (avg_ms * 1e-3) / HBM_PEAK_BYTES,
+                           "traffic_over_algorithmic": (traffic / bytes_launch) if traffic else None,
+                           "gemm_share_of_step": 2.0 * avg_ms * 1e-3 * K / dt}
+        out["checks"] = chk
     if cold is not None:
         out["cold_start"] = {"value": K / cold, "ms_per_step": 1e3 * cold / K,
                              "note": f"the same W + K steps in the cold process, before the {preheat} untimed pre-heating iterations after which the factors were "
@@ -856,7 +903,7 @@ def main():
             d["ideal_vs_achieved"] = {"ideal_ms_per_step": local_floor, "achieved_ms_per_step": 1e3 * dt / K, "ratio": local_floor / (1e3 * dt / K),
                                       "note": "ideal = this rank's rows through the single-GPU loop, no exchange (max over ranks); achieved = `ms_per_step`"}
         out["distributed"] = d
-    if world == 1 and not sharded and args.secondary:
+    if world == 1 and not sharded and args.secondary and full:
         sec = {}
         # another operand format, same data and schedule; the difference of the final factors between the two runs is reported
         if args.alt_operands not in ("none", args.operands):
@@ -915,7 +962,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             sec["widened_engines"] = {"error": f"{type(e).__name__}: {e}"}
         out["secondary"] = sec
-    if world == 1 and args.cpu_rows != 0:
+    if world == 1 and args.cpu_rows != 0 and full:
         out["cpu_baseline"] = cpu_baseline(X, U0, V0, reg0, m)
     if sus is not None:
         out["sustained"] = sus

@@ -4,9 +4,9 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$1; mkdir -p $OUT
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cut -c1-300 $OUT/bench.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --cpu-rows 0 --traffic 0 > $OUT/bench_under_profiler.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --full --cpu-rows 0 --traffic 0 > $OUT/bench_under_profiler.log 2>&1
 cp $OUT/stats/*/*kernel_stats.csv $OUT/kernel_stats.csv
 scripts/trace_i8.sh $1/headline_only --traffic 0 > $OUT/headline_only_summary.txt 2>&1
 cp $OUT/headline_only/*/*kernel_stats.csv $OUT/kernel_stats_headline_only.csv

@@ -3,7 +3,7 @@
 # --kernel-trace only (one TCC counter group per pass).  usage (GPU box): bash scripts/pmc_mae.sh
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmcmae2; rm -rf $OUT; mkdir -p $OUT
-ARGS="bench.py --steps 6 --warmup 2 --cpu-rows 0 --alt-operands none --mae 1"
+ARGS="bench.py --full --steps 6 --warmup 2 --cpu-rows 0 --alt-operands none --mae 1"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d $OUT/sq -- python3 $ARGS > $OUT/sq.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- python3 $ARGS > $OUT/fetch.log 2>&1
 python3 - <<PY

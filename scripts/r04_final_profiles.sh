@@ -3,6 +3,7 @@
 # box via gpurun; the copies into profiles/ are made afterwards from gpurun_out/final4/).   r04_final_profiles.sh [part ...]   parts: bench stats shards c2 c5 widened parity
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
+REPO=$PWD
 OUT=gpurun_out/final4; mkdir -p $OUT
 export TMPDIR=/tmp
 PARTS="${@:-bench stats shards c2 c5 widened parity}"
@@ -19,13 +20,13 @@ for row in csv.DictReader(open(f)):
 PY
 }
 if has bench; then   # the default bench line (what the driver runs), twice
-  timeout -k 10 550 python bench.py > $OUT/bench_default_a.json 2> $OUT/bench_default_a.err; echo "bench a rc $?"
-  timeout -k 10 550 python bench.py > $OUT/bench_default_b.json 2> $OUT/bench_default_b.err; echo "bench b rc $?"
+  timeout -k 10 550 python bench.py --full > $OUT/bench_default_a.json 2> $OUT/bench_default_a.err; echo "bench a rc $?"
+  timeout -k 10 550 python bench.py --full > $OUT/bench_default_b.json 2> $OUT/bench_default_b.err; echo "bench b rc $?"
 fi
 if has stats; then   # kernel statistics of the headline loop alone and with the MAE pass
   rm -rf $OUT/prof_headline $OUT/prof_mae
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof_headline -- python3 $GRAFT_REPO_ROOT/bench.py --steps 60 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 > $GRAFT_REPO_ROOT/$OUT/prof_headline.log 2>&1)
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof_mae -- python3 $GRAFT_REPO_ROOT/bench.py --steps 60 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 --mae 1 > $GRAFT_REPO_ROOT/$OUT/prof_mae.log 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_headline -- python3 $REPO/bench.py --full --steps 60 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 > $REPO/$OUT/prof_headline.log 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_mae -- python3 $REPO/bench.py --full --steps 60 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 --mae 1 > $REPO/$OUT/prof_mae.log 2>&1)
   stats_table $OUT/prof_headline | tee $OUT/prof_headline.txt; stats_table $OUT/prof_mae | tee $OUT/prof_mae.txt
 fi
 if has shards; then scripts/r04_shard_sizes.sh | tee $OUT/shard_sizes.txt; fi

@@ -3,7 +3,7 @@
 # (RCCL with one rank).  Every timed leg of a run is printed, so that a one-off host cost in one of them shows.  r04_shard_sizes.sh [sizes]
 for mm in ${1:-100000 50000 25000 12500}; do
   for mode in 0 1; do
-    BMF_FORCE_SHARDED=$mode timeout -k 10 200 python bench.py --m $mm --steps 30 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 --repeat 3 2>/dev/null | tail -1 | python -c "
+    BMF_FORCE_SHARDED=$mode timeout -k 10 200 python bench.py --full --m $mm --steps 30 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 --repeat 3 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); dd=d.get('distributed',{}) or {}
 legs=[1e3/x for x in d.get('repeat',{}).get('legs_of_K_steps',[])]

@@ -12,7 +12,7 @@ else
   mkdir -p gpurun_out/r05
   for name in base $(for sp in $SPECS; do echo ${sp%%:*}; done) base; do
     lib=libbmf_prio_$name.so; [ "$name" = base ] && lib=libbmf_hip.so
-    BMF_LIB=$lib timeout -k 10 200 python bench.py --steps 30 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 3000 --repeat 3 2>/dev/null \
+    BMF_LIB=$lib timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 3000 --repeat 3 2>/dev/null \
       | python3 -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('$name', 'value', round(d['value'],1), 'repeat', [round(v,1) for v in d['repeat']['legs_of_K_steps']], 'sustained', round(d.get('sustained',{}).get('value',0),1), 'gemm ms', d['roofline'].get('avg_launch_ms'))"
   done
 fi

@@ -2,10 +2,11 @@
 # Round 5: kernel statistics of the headline loop at a given row count (rocprofv3 --kernel-trace --stats): r05_kernel_stats.sh M [NAME] [ENV=VAL ...]
 #   -> gpurun_out/r05/kernel_stats_NAME.csv (+ a one-line-per-kernel table on stdout)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+REPO=$PWD
 M=${1:-100000}; NAME=${2:-m$M}; shift; shift
 for kv in "$@"; do export "$kv"; done
 OUT=gpurun_out/r05/prof_$NAME; rm -rf $OUT; mkdir -p $OUT
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT -- python3 $GRAFT_REPO_ROOT/bench.py --m $M --steps 60 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 > $GRAFT_REPO_ROOT/$OUT.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT -- python3 $REPO/bench.py --full --m $M --steps 60 --warmup 5 --cpu-rows 0 --traffic 0 --secondary 0 --sustained 0 > $REPO/$OUT.log 2>&1)
 cp $OUT/*/*kernel_stats.csv gpurun_out/r05/kernel_stats_$NAME.csv
 python3 - <<PY
 import csv

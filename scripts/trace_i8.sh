@@ -2,7 +2,7 @@
 # kernel-trace of the bench: per-dispatch durations of the bits GEMM in launch order (X V and X^T U alternate).  usage: trace_i8.sh OUT [bench args]
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$1; shift; rm -rf $OUT; mkdir -p $(dirname $OUT)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 20 --warmup 3 --cpu-rows 0 --alt-operands none --secondary 0 "$@" > $OUT.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --steps 20 --warmup 3 --cpu-rows 0 --alt-operands none --secondary 0 "$@" > $OUT.log 2>&1
 grep -h metric $OUT.log | cut -c1-150
 python3 - <<PY
 import csv,glob,collections

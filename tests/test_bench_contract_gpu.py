@@ -12,10 +12,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line():
+    """--full: every figure beyond the headline is on the line."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--m", "6000", "--n", "3000",
-           "--k", "64", "--traffic", "0"]
+           "--k", "64", "--traffic", "0", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -53,8 +54,46 @@ def test_bench_without_preheat():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--m", "3000", "--n", "2000",
-           "--k", "64", "--traffic", "0", "--secondary", "0", "--cpu-rows", "0", "--preheat", "0"]
+           "--k", "64", "--traffic", "0", "--secondary", "0", "--cpu-rows", "0", "--preheat", "0", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert "cold_start" not in d and "preheat_iterations" not in d["config"] and d["final"]["iter"] == 4
+
+
+def run_plain(out_dir, steps=4, warmup=2):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--m", "6000",
+           "--n", "3000", "--k", "64", "--dump-outputs", str(out_dir)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run: the headline only (no --full parts), exactly K timed steps, and --dump-outputs writes the timed loop's factors and
+    log table after its last step; the same arguments give the same inputs, hence the same outputs."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import numpy as np
+    K, W = 4, 2
+    d = run_plain(tmp_path / "a", K, W)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "final"):
+        assert key in d, key
+    for key in ("roofline", "cpu_baseline", "secondary", "checks", "repeat", "sustained", "cold_start", "alt", "with_mae", "updates_only"):
+        assert key not in d, key
+    assert d["steps"] == K and d["warmup"] == W and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=1e-9) and d["final"]["iter"] == W + K
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["U.npy", "V.npy", "log.npy"], files
+    U, V, log = (np.load(tmp_path / "a" / f) for f in ("U.npy", "V.npy", "log.npy"))
+    assert U.shape == (6000, 64) and V.shape == (3000, 64) and log.shape == (1 + W + K, 10)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in (U, V, log))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    assert log[-1, 0] == W + K and log[-1, 1] == pytest.approx(d["final"]["error"], rel=1e-12)
+    assert (log[-1, 6], log[-1, 7]) == (d["final"]["TP"], d["final"]["FP"])   # (columns: iter, error, rec, reg, reg_error, RMSE, TP, FP, FN, TN)
+    d2 = run_plain(tmp_path / "b", K, W)
+    assert d2["final"] == pytest.approx(d["final"], rel=1e-9)
+    for f in files:
+        np.testing.assert_allclose(np.load(tmp_path / "b" / f), np.load(tmp_path / "a" / f), rtol=1e-9, atol=0, err_msg=f)

@@ -229,3 +229,23 @@ def test_movielens_loader_follows_the_reference_recipe(tmp_path):
     X = bench.load_movielens_1m(str(p))
     assert X.dtype == np.uint8 and X.tolist() == [[0, 0, 1], [1, 0, 0], [0, 1, 1]]      # users 1, 3, 5 x items 7, 10, 20
     assert bench.load_movielens_1m(str(tmp_path / "absent.dat")) is None
+
+
+def test_dump_outputs_samples_rows_within_the_limit(tmp_path):
+    """More than the limit in all: the large arrays keep a fixed, seeded, sorted row sample; the small ones are written whole."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rs = np.random.RandomState(0)
+    arrays = [("log", rs.rand(7, 11)), ("V", rs.rand(3000, 64)), ("U", rs.rand(20000, 64))]
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, limit=4 * 10 ** 6)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 4 * 10 ** 6
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "log.npy"), arrays[0][1])
+    for name, a in arrays[1:]:
+        rows = np.load(tmp_path / "a" / f"{name}_rows.npy").astype(np.int64)
+        assert len(rows) < a.shape[0] and (np.diff(rows) > 0).all()
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{name}.npy"), a[rows])
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{name}_rows.npy"), rows)

@@ -1,12 +1,14 @@
-"""Differential checks of the HOST-side pieces against the reference itself, imported from /root/reference when that exists
-(the build container; never on the GPU box -- the tests skip there).  Golden vectors pin fixed cases; these run the two
-implementations side by side on randomised inputs: the synthetic generator (bit-identical matrices), the line search and
-its step limiter, the stopping rule with its messages, and the container helpers of utils.  Nothing here touches the GPU."""
+"""Differential checks of the HOST-side pieces against the reference itself, on randomised inputs: the synthetic generator
+(bit-identical matrices), the line search and its step limiter, the stopping rule with its messages, the container helpers of
+utils, and the oracle against the reference's model classes.  The inputs are drawn here from fixed seeds; what the reference
+returned for each of them is stored in `golden/g21_differential.{npz,json}` (recorded by `golden/make_golden.py`, which runs the
+`record_*` functions below against the reference), so nothing here needs the reference at run time.  Nothing here touches the GPU."""
 import contextlib
+import hashlib
 import io
 import itertools
+import json
 import os
-import sys
 import warnings
 
 import numpy as np
@@ -14,17 +16,24 @@ import pytest
 from scipy.sparse import csc_matrix, csr_matrix, issparse, lil_matrix
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/PyBMF"), reason="the reference is only mounted in the build container")
+GOLDEN_STEM = os.path.join(HERE, "golden", "g21_differential")
 
 
 @pytest.fixture(scope="module")
 def ref():
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    import make_golden as mg
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        mg.load_reference()
-    return sys.modules
+    """What the reference returned, by key: arrays from the .npz, everything else (error names, messages, scalars) from the .json."""
+    with open(GOLDEN_STEM + ".json") as f:
+        rec = json.load(f)
+    with np.load(GOLDEN_STEM + ".npz") as z:
+        rec.update({k: z[k] for k in z.files})
+    return rec
+
+
+def save_records(rec, stem=GOLDEN_STEM):
+    arrays = {k: v for k, v in rec.items() if isinstance(v, np.ndarray)}
+    np.savez_compressed(stem + ".npz", **arrays)
+    with open(stem + ".json", "w") as f:
+        json.dump({k: v for k, v in rec.items() if k not in arrays}, f, sort_keys=True)
 
 
 def outcome(fn, *args, **kw):
@@ -41,32 +50,61 @@ def dense(x):
     return np.asarray(x.todense()) if issparse(x) else np.asarray(x)
 
 
-def test_generator_is_bit_identical(ref):
-    from PyBMF.generators import SyntheticMatrixGenerator as R
-    from pybmf_amd.generators import SyntheticMatrixGenerator as M
+def plain(x):
+    """A JSON value for a scalar / None / string returned by either implementation (numpy scalars as Python scalars)."""
+    return x.item() if isinstance(x, np.generic) else x
+
+
+def digest(arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(repr((a.shape, a.dtype.str)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+# ---- the synthetic generator -----------------------------------------------------------------------------------------------
+def generator_cases():
     rs = np.random.RandomState(5)
     for _ in range(25):
         m, n, k = int(rs.randint(1, 300)), int(rs.randint(1, 300)), int(rs.randint(1, 12))
         dens = [float(rs.uniform(0.02, 0.6)), float(rs.uniform(0.02, 0.6))]
         seed, nseed = int(rs.randint(0, 10 ** 6)), int(rs.randint(0, 10 ** 6))
         noise = [float(rs.uniform(0, 0.2)), float(rs.uniform(0, 0.1))]
-        got = []
-        for G in (R, M):
-            def run():
-                g = G(m=m, n=n, k=k, density=dens)
-                g.generate(seed=seed)
-                clean = dense(g.X).astype(np.uint8)
-                g.add_noise(noise=noise, seed=nseed)
-                return clean, dense(g.X).astype(np.uint8), dense(g.U).astype(np.uint8), dense(g.V).astype(np.uint8)
-            got.append(outcome(run))
-        (a, _, ea), (b, _, eb) = got
-        assert ea == eb, (m, n, k, ea, eb)
+        yield m, n, k, dens, seed, nseed, noise
+
+
+def generator_outcome(G, m, n, k, dens, seed, nseed, noise):
+    """(error name, SHA-256 of the clean X, noisy X, U and V as uint8 arrays)."""
+    def run():
+        g = G(m=m, n=n, k=k, density=dens)
+        g.generate(seed=seed)
+        clean = dense(g.X).astype(np.uint8)
+        g.add_noise(noise=noise, seed=nseed)
+        return clean, dense(g.X).astype(np.uint8), dense(g.U).astype(np.uint8), dense(g.V).astype(np.uint8)
+    r, _, err = outcome(run)
+    return err, (None if err else digest(r))
+
+
+def record_generator(rec):
+    from PyBMF.generators import SyntheticMatrixGenerator as R
+    for i, case in enumerate(generator_cases()):
+        rec[f"gen/{i}"] = list(generator_outcome(R, *case))
+
+
+def test_generator_is_bit_identical(ref):
+    from pybmf_amd.generators import SyntheticMatrixGenerator as M
+    for i, case in enumerate(generator_cases()):
+        ea, ha = ref[f"gen/{i}"]
+        eb, hb = generator_outcome(M, *case)
+        assert ea == eb, (case, ea, eb)
         if ea is None:
-            assert all(np.array_equal(x, y) for x, y in zip(a, b)), (m, n, k, dens, seed, nseed, noise)
+            assert ha == hb, case
 
 
-def test_line_search_and_step_limit(ref):
-    Rm, Mm = ref["PyBMF.solvers.line_search"], __import__("pybmf_amd.solvers.line_search", fromlist=["x"])
+# ---- the line search and its step limiter ----------------------------------------------------------------------------------
+def line_search_cases():
     rs = np.random.RandomState(0)
     for t in range(200):
         A = rs.rand(2, 2)
@@ -76,30 +114,47 @@ def test_line_search_and_step_limit(ref):
                 (lambda x: np.sum((x - b) ** 4) + 0.1 * np.sum(x ** 2), lambda x: 4 * (x - b) ** 3 + 0.2 * x)][t % 3]
         xk = rs.rand(2)
         pk = -g(xk)
-        (r, _, er), (m, _, em) = outcome(Rm.line_search, f, g, xk, pk), outcome(Mm.line_search, f, g, xk, pk)
-        assert er == em
-        if er is None:
-            for x, y in zip(r, m):
-                assert (x is None and y is None) or np.allclose(np.asarray(x, float), np.asarray(y, float), rtol=1e-12, equal_nan=True)
-    flat = lambda z: np.concatenate([np.ravel(np.asarray(q, float)) for q in (z if isinstance(z, (tuple, list)) else [z])])  # noqa: E731
+        yield "ls", (f, g, xk, pk)
     for _ in range(1000):
         x_min, x_max = sorted(rs.rand(2) * 2 - 0.5)
-        args = (x_min, x_max, rs.rand(2), rs.rand(2) * 1.5 - 0.25, rs.rand() * 3, rs.randn(2))
-        (r, _, er), (m, _, em) = outcome(Rm.limit_step_size, *args), outcome(Mm.limit_step_size, *args)
-        assert er == em and (er is not None or np.allclose(flat(r), flat(m), rtol=1e-13, equal_nan=True)), args
+        yield "limit", (x_min, x_max, rs.rand(2), rs.rand(2) * 1.5 - 0.25, rs.rand() * 3, rs.randn(2))
 
 
-def test_stopping_rule_and_its_messages(ref):
-    from PyBMF.models.BaseModelTools import BaseModelTools as R
-    from pybmf_amd.models.BaseModelTools import BaseModelTools as M
+def flat(z):
+    return np.concatenate([np.ravel(np.asarray(q, float)) for q in (z if isinstance(z, (tuple, list)) else [z])])
 
-    class RP(R):
-        def __init__(self):
-            pass
 
-    class MP(M):
-        def __init__(self):
-            pass
+def line_search_outcome(mod, kind, args):
+    """(error name, result): the line search's tuple with None kept, the limiter's result flattened."""
+    if kind == "ls":
+        r, _, err = outcome(mod.line_search, *args)
+        return err, (None if err else [None if x is None else np.asarray(x, float).tolist() for x in r])
+    r, _, err = outcome(mod.limit_step_size, *args)
+    return err, (None if err else flat(r).tolist())
+
+
+def record_line_search(rec):
+    import importlib
+    R = importlib.import_module("PyBMF.solvers.line_search")   # (the package re-exports a function of the same name)
+    for i, (kind, args) in enumerate(line_search_cases()):
+        rec[f"ls/{i}"] = list(line_search_outcome(R, kind, args))
+
+
+def test_line_search_and_step_limit(ref):
+    M = __import__("pybmf_amd.solvers.line_search", fromlist=["x"])
+    for i, (kind, args) in enumerate(line_search_cases()):
+        er, r = ref[f"ls/{i}"]
+        em, m = line_search_outcome(M, kind, args)
+        assert er == em, (kind, i, er, em)
+        if er is None and kind == "ls":
+            for x, y in zip(r, m):
+                assert (x is None and y is None) or np.allclose(np.asarray(x, float), np.asarray(y, float), rtol=1e-12, equal_nan=True)
+        elif er is None:
+            assert np.allclose(np.asarray(r, float), np.asarray(m, float), rtol=1e-13, equal_nan=True), args
+
+
+# ---- the stopping rule -----------------------------------------------------------------------------------------------------
+def stopping_cases():
     rs = np.random.RandomState(3)
     for _ in range(2000):
         attrs, kw = {}, {}
@@ -119,53 +174,95 @@ def test_stopping_rule_and_its_messages(ref):
             kw["n_iter"] = int(rs.choice([0, 1, 2, 6, 101]))
         if rs.rand() < 0.2:
             kw["n_factor"] = int(rs.choice([1, 3, 4]))
-        res = []
-        for P in (RP, MP):
-            p = P()
-            for a, v in attrs.items():
-                setattr(p, a, v)
-            res.append(outcome(p.early_stop, **kw))
-        assert res[0] == res[1], (attrs, kw, res)
+        yield attrs, kw
 
 
-def test_container_helpers(ref):
-    import PyBMF.utils as R
-    import pybmf_amd.utils as M
+def stopping_outcome(Base, attrs, kw):
+    class P(Base):
+        def __init__(self):
+            pass
+    p = P()
+    for a, v in attrs.items():
+        setattr(p, a, v)
+    r, out, err = outcome(p.early_stop, **kw)
+    return plain(r), out, err
+
+
+def record_stopping_rule(rec):
+    from PyBMF.models.BaseModelTools import BaseModelTools as R
+    for i, (attrs, kw) in enumerate(stopping_cases()):
+        rec[f"stop/{i}"] = list(stopping_outcome(R, attrs, kw))
+
+
+def test_stopping_rule_and_its_messages(ref):
+    from pybmf_amd.models.BaseModelTools import BaseModelTools as M
+    for i, (attrs, kw) in enumerate(stopping_cases()):
+        want, got = tuple(ref[f"stop/{i}"]), stopping_outcome(M, attrs, kw)
+        assert want == got, (attrs, kw, want, got)
+
+
+# ---- the container helpers of utils ----------------------------------------------------------------------------------------
+def container_calls(U):
+    """Every (name, function, args, kwargs) of the comparison, drawn from one seed; U = the utils module under test."""
     rs = np.random.RandomState(0)
 
     def forms(A):
         return [A, csr_matrix(A), lil_matrix(A), csc_matrix(A)]
-
-    def same(name, fr, fm, *args, **kw):
-        (r, _, er), (m, _, em) = outcome(fr, *args, **kw), outcome(fm, *args, **kw)
-        assert er == em, (name, er, em)
-        if er is None:
-            assert type(r).__name__ == type(m).__name__ or (issparse(r) and issparse(m) and r.format == m.format), (name, type(r), type(m))
-            assert np.allclose(dense(r).astype(float), dense(m).astype(float), equal_nan=True), name
     A, B, C = ((rs.rand(*s) < 0.4).astype(float) for s in ((7, 5), (7, 5), (5, 6)))
     for a, b in itertools.product(forms(A), forms(B)):
         for boolean in (False, True):
-            same("multiply", R.multiply, M.multiply, a, b, boolean=boolean)
-            same("add", R.add, M.add, a, b, boolean=boolean)
+            yield "multiply", U.multiply, (a, b), dict(boolean=boolean)
+            yield "add", U.add, (a, b), dict(boolean=boolean)
     for a, c in itertools.product(forms(A), forms(C)):
         for boolean, sparse in itertools.product((False, True), (False, True)):
-            same("matmul", R.matmul, M.matmul, a, c, boolean=boolean, sparse=sparse)
+            yield "matmul", U.matmul, (a, c), dict(boolean=boolean, sparse=sparse)
     u, v = A[:, 0], B[:, 0]
     for a, b in itertools.product([u, csr_matrix(u), lil_matrix(u)], [v, csr_matrix(v)]):
         for boolean in (False, True):
-            same("dot", R.dot, M.dot, a, b, boolean=boolean)
+            yield "dot", U.dot, (a, b), dict(boolean=boolean)
     for a in forms(rs.rand(7, 5)):
-        same("power", R.power, M.power, a, 2)
-        same("sigmoid", R.sigmoid, M.sigmoid, a)
-        same("d_sigmoid", R.d_sigmoid, M.d_sigmoid, a)
-        same("to_dense", R.to_dense, M.to_dense, a)
-        same("binarize", R.binarize, M.binarize, a, 0.5)
-        same("to_triplet", lambda x: np.array(R.to_triplet(x)), lambda x: np.array(M.to_triplet(x)), a)
+        yield "power", U.power, (a, 2), {}
+        yield "sigmoid", U.sigmoid, (a,), {}
+        yield "d_sigmoid", U.d_sigmoid, (a,), {}
+        yield "to_dense", U.to_dense, (a,), {}
+        yield "binarize", U.binarize, (a, 0.5), {}
+        yield "to_triplet", lambda x: np.array(U.to_triplet(x)), (a,), {}
         for fmt in ("csr", "lil", "csc"):
-            same("to_sparse", R.to_sparse, M.to_sparse, a, fmt)
+            yield "to_sparse", U.to_sparse, (a, fmt), {}
     for a in (A, csr_matrix(A)):      # matrix - constant (matrix - matrix cannot be reached in the reference: see utils.subtract)
-        same("subtract", R.subtract, M.subtract, a, 1.0)
-        same("subtract", R.subtract, M.subtract, 1.0, a)
+        yield "subtract", U.subtract, (a, 1.0), {}
+        yield "subtract", U.subtract, (1.0, a), {}
+
+
+def container_outcome(fn, args, kw):
+    """(error name, type name, is sparse, sparse format, dense value as float)."""
+    r, _, err = outcome(fn, *args, **kw)
+    if err:
+        return err, None, None, None, None
+    return None, type(r).__name__, bool(issparse(r)), (r.format if issparse(r) else None), dense(r).astype(float)
+
+
+def record_container_helpers(rec):
+    import PyBMF.utils as R
+    for i, (name, fn, args, kw) in enumerate(container_calls(R)):
+        err, tname, sp, fmt, val = container_outcome(fn, args, kw)
+        rec[f"util/{i}"] = [name, err, tname, sp, fmt]
+        if err is None:
+            rec[f"util/{i}/value"] = val
+
+
+def test_container_helpers(ref):
+    import pybmf_amd.utils as M
+    n = 0
+    for i, (name, fn, args, kw) in enumerate(container_calls(M)):
+        rname, er, rtype, rsparse, rfmt = ref[f"util/{i}"]
+        em, mtype, msparse, mfmt, mval = container_outcome(fn, args, kw)
+        assert rname == name and er == em, (name, er, em)
+        if er is None:
+            assert rtype == mtype or (rsparse and msparse and rfmt == mfmt), (name, rtype, mtype)
+            assert np.allclose(ref[f"util/{i}/value"], mval, equal_nan=True), name
+        n += 1
+    assert f"util/{n}" not in ref   # (as many calls as were recorded)
 
 
 # ---- the oracle itself against the reference's classes, on random small problems -------------------------------------------
@@ -206,9 +303,7 @@ def random_mask(rs, X, weights):
     return W
 
 
-def test_oracle_penalty_fit_against_the_reference(ref):
-    import oracle as orc
-    from PyBMF.models import BinaryMFPenalty
+def penalty_cases():
     rs = np.random.RandomState(11)
     for t in range(12):
         m, n, k, X, U0, V0 = random_problem(rs)
@@ -216,6 +311,12 @@ def test_oracle_penalty_fit_against_the_reference(ref):
         mode = t % 2   # all-ones mask / W='mask' on a csr with explicit zeros.  (A weight MATRIX cannot be given to the reference:
         #                  its `self.W in ['mask', 'full']` check raises on an ndarray and on scipy sparse alike.)
         W = None if mode == 0 else random_mask(rs, X, weights=False)
+        yield t, mode, m, n, k, X, U0, V0, reg, growth, iters, W
+
+
+def record_penalty_fit(rec):
+    from PyBMF.models import BinaryMFPenalty
+    for t, mode, m, n, k, X, U0, V0, reg, growth, iters, W in penalty_cases():
         if mode == 1:
             r, c = np.nonzero(W)
             data, Wref = csr_matrix((X[r, c], (r, c)), shape=(m, n)), "mask"
@@ -223,75 +324,111 @@ def test_oracle_penalty_fit_against_the_reference(ref):
             data, Wref = X.copy(), "full"
         mdl = quiet_fit(BinaryMFPenalty(k=k, U=U0.copy(), V=V0.copy(), W=Wref, reg=reg, reg_growth=growth, init_method="custom",
                                         normalize_method="balance", max_iter=iters, tol=-1.0), data)
+        rec[f"pen/{t}/U"], rec[f"pen/{t}/V"] = np.asarray(mdl.U, float), np.asarray(mdl.V, float)
+        rec[f"pen/{t}/updates"], rec[f"pen/{t}/boolean"] = frame(mdl.logs["updates"]), frame(mdl.logs["boolean"])
+
+
+def test_oracle_penalty_fit_against_the_reference(ref):
+    import oracle as orc
+    for t, mode, m, n, k, X, U0, V0, reg, growth, iters, W in penalty_cases():
         got = orc.penalty_fit(X * (W != 0) if W is not None else X, k=k, U=U0.copy(), V=V0.copy(), reg=reg, reg_growth=growth,
                               init_method="custom", normalize_method="balance", max_iter=iters, tol=-1.0, W=W)
-        np.testing.assert_allclose(got["U"], np.asarray(mdl.U), rtol=1e-9, atol=1e-300, err_msg=str((t, mode)))
-        np.testing.assert_allclose(got["V"], np.asarray(mdl.V), rtol=1e-9, atol=1e-300)
-        np.testing.assert_allclose(np.array(got["updates"]), frame(mdl.logs["updates"]), rtol=1e-9)
-        np.testing.assert_allclose(np.array(got["boolean"]), frame(mdl.logs["boolean"]), rtol=1e-13, atol=0)
+        np.testing.assert_allclose(got["U"], ref[f"pen/{t}/U"], rtol=1e-9, atol=1e-300, err_msg=str((t, mode)))
+        np.testing.assert_allclose(got["V"], ref[f"pen/{t}/V"], rtol=1e-9, atol=1e-300)
+        np.testing.assert_allclose(np.array(got["updates"]), ref[f"pen/{t}/updates"], rtol=1e-9)
+        np.testing.assert_allclose(np.array(got["boolean"]), ref[f"pen/{t}/boolean"], rtol=1e-13, atol=0)
 
 
-def test_oracle_wnmf_fits_against_the_reference(ref):
-    import oracle as orc
-    from PyBMF.models import WNMF
+def wnmf_cases():
     rs = np.random.RandomState(12)
     for t in range(12):
         m, n, k, X, U0, V0 = random_problem(rs, real=(t % 2 == 0))
         iters = int(rs.randint(1, 5))
         W = None if t % 3 == 0 else random_mask(rs, X, weights=False)
-        if W is None:
-            data, Wref = X.copy(), "full"
-        else:
-            r, c = np.nonzero(W)
-            data, Wref = csr_matrix((X[r, c], (r, c)), shape=(m, n)), "mask"
-        mdl = quiet_fit(WNMF(k=k, U=U0.copy(), V=V0.copy(), W=Wref, init_method="custom", max_iter=iters, tol=-1.0), data)
-        got = orc.wnmf_fit(X.copy(), k, U=U0.copy(), V=V0.copy(), W=W, max_iter=iters, init_method="custom", tol=-1.0)
-        np.testing.assert_allclose(got["U"], np.asarray(mdl.U), rtol=1e-9, atol=1e-300, err_msg=str(t))
-        np.testing.assert_allclose(got["V"], np.asarray(mdl.V), rtol=1e-9, atol=1e-300)
-        np.testing.assert_allclose(np.array(got["updates"]), frame(mdl.logs["updates"]), rtol=1e-9)
+        yield "fro", t, m, n, k, X, U0, V0, iters, W
     for t in range(6):   # Kullback-Leibler, Boolean X with every row and column non-empty
         m, n, k, X, U0, V0 = random_problem(rs)
         X[np.arange(m), rs.randint(n, size=m)] = 1.0
         X[rs.randint(m, size=n), np.arange(n)] = 1.0
         iters = int(rs.randint(1, 4))
-        masked = t % 2 == 1
-        mdl = quiet_fit(WNMF(k=k, U=U0.copy(), V=V0.copy(), W="mask" if masked else "full", beta_loss="kullback-leibler", init_method="custom",
-                             max_iter=iters), X.copy())
-        got = orc.wnmf_kl_fit(X.copy(), k, U=U0.copy(), V=V0.copy(), W=(X != 0).astype(np.float64) if masked else None, max_iter=iters,
-                              init_method="custom")
-        np.testing.assert_allclose(got["U"], np.asarray(mdl.U), rtol=1e-9, atol=1e-300, err_msg=str(t))
-        np.testing.assert_allclose(np.array(got["updates"]), frame(mdl.logs["updates"]), rtol=1e-9)
+        yield "kl", t, m, n, k, X, U0, V0, iters, t % 2 == 1
 
 
-def test_oracle_pnlpf_and_threshold_against_the_reference(ref):
+def record_wnmf_fits(rec):
+    from PyBMF.models import WNMF
+    for kind, t, m, n, k, X, U0, V0, iters, W in wnmf_cases():
+        if kind == "fro":
+            if W is None:
+                data, Wref = X.copy(), "full"
+            else:
+                r, c = np.nonzero(W)
+                data, Wref = csr_matrix((X[r, c], (r, c)), shape=(m, n)), "mask"
+            mdl = quiet_fit(WNMF(k=k, U=U0.copy(), V=V0.copy(), W=Wref, init_method="custom", max_iter=iters, tol=-1.0), data)
+            rec[f"wnmf/{t}/V"] = np.asarray(mdl.V, float)
+        else:
+            mdl = quiet_fit(WNMF(k=k, U=U0.copy(), V=V0.copy(), W="mask" if W else "full", beta_loss="kullback-leibler", init_method="custom",
+                                 max_iter=iters), X.copy())
+        rec[f"{kind}/{t}/U"], rec[f"{kind}/{t}/updates"] = np.asarray(mdl.U, float), frame(mdl.logs["updates"])
+
+
+def test_oracle_wnmf_fits_against_the_reference(ref):
     import oracle as orc
-    from PyBMF.models import PNLPF, BinaryMFThreshold
+    for kind, t, m, n, k, X, U0, V0, iters, W in wnmf_cases():
+        if kind == "fro":
+            got = orc.wnmf_fit(X.copy(), k, U=U0.copy(), V=V0.copy(), W=W, max_iter=iters, init_method="custom", tol=-1.0)
+            np.testing.assert_allclose(got["V"], ref[f"wnmf/{t}/V"], rtol=1e-9, atol=1e-300)
+        else:
+            got = orc.wnmf_kl_fit(X.copy(), k, U=U0.copy(), V=V0.copy(), W=(X != 0).astype(np.float64) if W else None, max_iter=iters,
+                                  init_method="custom")
+        np.testing.assert_allclose(got["U"], ref[f"{kind}/{t}/U"], rtol=1e-9, atol=1e-300, err_msg=str((kind, t)))
+        np.testing.assert_allclose(np.array(got["updates"]), ref[f"{kind}/{t}/updates"], rtol=1e-9)
+
+
+def pnlpf_threshold_cases():
     rs = np.random.RandomState(13)
     for t in range(6):
         m, n, k, X, U0, V0 = random_problem(rs)
         iters, lam = int(rs.randint(1, 4)), float(rs.choice([5, 10, 20]))
-        mdl = quiet_fit(PNLPF(k=k, U=U0.copy(), V=V0.copy(), W="full", reg=1.0, link_lamda=lam, reg_growth=1.2, init_method="custom",
-                              normalize_method="balance", max_iter=iters, tol=-1.0), X.copy())
-        got = orc.pnlpf_fit(X, k=k, U=U0.copy(), V=V0.copy(), reg=1.0, link_lamda=lam, reg_growth=1.2, init_method="custom",
-                            normalize_method="balance", max_iter=iters, tol=-1.0)
-        np.testing.assert_allclose(got["U"], np.asarray(mdl.U), rtol=1e-9, atol=1e-300, err_msg=str(t))
-        np.testing.assert_allclose(np.array(got["updates"]), frame(mdl.logs["updates"]), rtol=1e-9)
-        np.testing.assert_allclose(np.array(got["boolean"]), frame(mdl.logs["boolean"]), rtol=1e-13, atol=0)
+        yield "pnlpf", t, k, X, U0, V0, dict(iters=iters, lam=lam)
     for t in range(6):
         m, n, k, X, _, _ = random_problem(rs)
         U, V = rs.rand(m, k), rs.rand(n, k)
         lam, u0, v0 = float(rs.choice([5, 10, 50])), float(rs.uniform(0.2, 0.8)), float(rs.uniform(0.2, 0.8))
-        mdl = quiet_fit(BinaryMFThreshold(k=k, U=U.copy(), V=V.copy(), W="full", u=u0, v=v0, lamda=lam, min_diff=1e-3, max_iter=15), X.copy())
-        got = orc.threshold_fit(X, U, V, None, u=u0, v=v0, lamda=lam, min_diff=1e-3, max_iter=15)
-        assert got["u"] == pytest.approx(float(mdl.u), rel=1e-9) and got["v"] == pytest.approx(float(mdl.v), rel=1e-9), t
-        np.testing.assert_allclose(np.array([r[:4] for r in got["rows"]]), frame(mdl.logs["updates"])[:, :4], rtol=1e-9)
+        yield "thr", t, k, X, U, V, dict(lam=lam, u0=u0, v0=v0)
 
 
-def test_oracle_entry_scores_against_the_reference(ref):
-    """task='prediction' with val / test sets: the columns the reference logs equal the oracle's entry scorer on the reference's
-    own factors (non-zero cells of each densified set; WNMF's train set: every cell, after its in-place eps write)."""
+def record_pnlpf_and_threshold(rec):
+    from PyBMF.models import PNLPF, BinaryMFThreshold
+    for kind, t, k, X, U0, V0, p in pnlpf_threshold_cases():
+        if kind == "pnlpf":
+            mdl = quiet_fit(PNLPF(k=k, U=U0.copy(), V=V0.copy(), W="full", reg=1.0, link_lamda=p["lam"], reg_growth=1.2, init_method="custom",
+                                  normalize_method="balance", max_iter=p["iters"], tol=-1.0), X.copy())
+            rec[f"pnlpf/{t}/U"] = np.asarray(mdl.U, float)
+            rec[f"pnlpf/{t}/updates"], rec[f"pnlpf/{t}/boolean"] = frame(mdl.logs["updates"]), frame(mdl.logs["boolean"])
+        else:
+            mdl = quiet_fit(BinaryMFThreshold(k=k, U=U0.copy(), V=V0.copy(), W="full", u=p["u0"], v=p["v0"], lamda=p["lam"], min_diff=1e-3,
+                                              max_iter=15), X.copy())
+            rec[f"thr/{t}/uv"] = [float(mdl.u), float(mdl.v)]
+            rec[f"thr/{t}/updates"] = frame(mdl.logs["updates"])[:, :4]
+
+
+def test_oracle_pnlpf_and_threshold_against_the_reference(ref):
     import oracle as orc
-    from PyBMF.models import BinaryMFPenalty, WNMF
+    for kind, t, k, X, U0, V0, p in pnlpf_threshold_cases():
+        if kind == "pnlpf":
+            got = orc.pnlpf_fit(X, k=k, U=U0.copy(), V=V0.copy(), reg=1.0, link_lamda=p["lam"], reg_growth=1.2, init_method="custom",
+                                normalize_method="balance", max_iter=p["iters"], tol=-1.0)
+            np.testing.assert_allclose(got["U"], ref[f"pnlpf/{t}/U"], rtol=1e-9, atol=1e-300, err_msg=str(t))
+            np.testing.assert_allclose(np.array(got["updates"]), ref[f"pnlpf/{t}/updates"], rtol=1e-9)
+            np.testing.assert_allclose(np.array(got["boolean"]), ref[f"pnlpf/{t}/boolean"], rtol=1e-13, atol=0)
+        else:
+            got = orc.threshold_fit(X, U0, V0, None, u=p["u0"], v=p["v0"], lamda=p["lam"], min_diff=1e-3, max_iter=15)
+            u, v = ref[f"thr/{t}/uv"]
+            assert got["u"] == pytest.approx(u, rel=1e-9) and got["v"] == pytest.approx(v, rel=1e-9), t
+            np.testing.assert_allclose(np.array([r[:4] for r in got["rows"]]), ref[f"thr/{t}/updates"], rtol=1e-9)
+
+
+def entry_score_cases():
     rs = np.random.RandomState(14)
     for t in range(8):
         m, n, k, X, U0, V0 = random_problem(rs)
@@ -302,15 +439,39 @@ def test_oracle_entry_scores_against_the_reference(ref):
             sets[nm] = csr_matrix((X[r, c], (r, c)), shape=(m, n))
         if any(s.nnz == 0 or s.data.sum() == 0 for s in sets.values()):
             continue
+        yield t, k, U0, V0, sets
+
+
+def record_entry_scores(rec):
+    """The reference's own factors after a task='prediction' fit, and the RMSE / MAE (and Boolean scores) it logged per set."""
+    from PyBMF.models import BinaryMFPenalty, WNMF
+    for t, k, U0, V0, sets in entry_score_cases():
         if t % 2 == 0:
             mdl = BinaryMFPenalty(k=k, U=U0.copy(), V=V0.copy(), W="mask", reg=0.5, reg_growth=1.3, init_method="custom", normalize_method=None,
                                   max_iter=2, tol=-1.0)
         else:
             mdl = WNMF(k=k, U=U0.copy(), V=V0.copy(), W="mask", init_method="custom", max_iter=2, tol=-1.0)
         quiet_fit(mdl, sets["train"].copy(), sets["val"].copy(), sets["test"].copy(), task="prediction")
-        U, V = np.asarray(mdl.U), np.asarray(mdl.V)
+        rec[f"entry/{t}/U"], rec[f"entry/{t}/V"] = np.asarray(mdl.U, float), np.asarray(mdl.V, float)
         cols = [tuple(str(x) for x in c) for c in mdl.logs["updates"].columns]
         row = mdl.logs["updates"].values.tolist()[-1]
+        logged = {f"{nm}/{mt}": float(row[cols.index((nm, "0", mt))]) for nm in ("train", "val", "test") for mt in ("RMSE", "MAE")}
+        if t % 2 == 0:
+            bcols = [tuple(str(x) for x in c) for c in mdl.logs["boolean"].columns]
+            brow = mdl.logs["boolean"].values.tolist()[-1]
+            logged.update({f"{nm}/{mt}": float(brow[bcols.index((nm, "0", mt))]) for nm in ("train", "val", "test")
+                           for mt in ("Recall", "Precision", "Accuracy", "F1")})
+        rec[f"entry/{t}/logged"] = logged
+
+
+def test_oracle_entry_scores_against_the_reference(ref):
+    """task='prediction' with val / test sets: the columns the reference logs equal the oracle's entry scorer on the reference's
+    own factors (non-zero cells of each densified set; WNMF's train set: every cell, after its in-place eps write)."""
+    import oracle as orc
+    n = 0
+    for t, k, U0, V0, sets in entry_score_cases():
+        U, V, logged = ref[f"entry/{t}/U"], ref[f"entry/{t}/V"], ref[f"entry/{t}/logged"]
+        n += 1
         for nm in ("train", "val", "test"):
             coo = sets[nm].tocoo()
             keep = coo.data != 0
@@ -318,22 +479,22 @@ def test_oracle_entry_scores_against_the_reference(ref):
                 want = orc.rmse_mae(sets[nm].toarray(), U @ V.T)
             else:
                 want = orc.entry_scores(coo.row[keep], coo.col[keep], coo.data[keep], U, V)
-            assert float(row[cols.index((nm, "0", "RMSE"))]) == pytest.approx(want[0], rel=1e-9), (t, nm)
-            assert float(row[cols.index((nm, "0", "MAE"))]) == pytest.approx(want[1], rel=1e-9), (t, nm)
+            assert logged[f"{nm}/RMSE"] == pytest.approx(want[0], rel=1e-9), (t, nm)
+            assert logged[f"{nm}/MAE"] == pytest.approx(want[1], rel=1e-9), (t, nm)
         if t % 2 == 0:
-            bcols = [tuple(str(x) for x in c) for c in mdl.logs["boolean"].columns]
-            brow = mdl.logs["boolean"].values.tolist()[-1]
             for nm in ("train", "val", "test"):
                 coo = sets[nm].tocoo()
                 keep = coo.data != 0
                 want = orc.boolean_scores(*orc.entry_scores(coo.row[keep], coo.col[keep], coo.data[keep], U, V, 0.5, 0.5))
-                got = [float(brow[bcols.index((nm, "0", mt))]) for mt in ("Recall", "Precision", "Accuracy", "F1")]
+                got = [logged[f"{nm}/{mt}"] for mt in ("Recall", "Precision", "Accuracy", "F1")]
                 np.testing.assert_allclose(got, want, rtol=1e-13)
+    assert n == sum(1 for key in ref if key.startswith("entry/") and key.endswith("/logged"))
 
 
-def test_oracle_metrics_against_the_reference(ref):
-    import oracle as orc
-    import PyBMF.utils as R
+METRIC_NAMES = ["TP", "FP", "TN", "FN", "Recall", "Precision", "Accuracy", "F1", "RMSE", "MAE"]
+
+
+def metric_cases():
     rs = np.random.RandomState(15)
     for t in range(40):
         m, n, k = int(rs.randint(1, 40)), int(rs.randint(1, 40)), int(rs.randint(1, 7))
@@ -341,28 +502,56 @@ def test_oracle_metrics_against_the_reference(ref):
         Ub, Vb = (rs.rand(m, k) < 0.3).astype(np.int64), (rs.rand(n, k) < 0.3).astype(np.int64)
         U, V = rs.rand(m, k), rs.rand(n, k)
         u, v = float(rs.uniform(0.2, 0.8)), float(rs.uniform(0.2, 0.8))
+        yield t, G, Ub, Vb, U, V, u, v
+
+
+def record_metrics(rec):
+    import oracle as orc
+    import PyBMF.utils as R
+    for t, G, Ub, Vb, U, V, u, v in metric_cases():
         (pr, _, er) = outcome(R.get_prediction_with_threshold, U=U, V=V, u=u, v=v)
         assert er is None
-        np.testing.assert_array_equal(dense(pr), orc.boolean_product(U, V, u, v))
+        rec[f"met/{t}/prediction"] = dense(pr).astype(np.float64)
         P = orc.boolean_product(Ub, Vb)
         Gs, Ps = csr_matrix(G), csr_matrix(P)
         for ax in (None, 0, 1):
-            want = [np.asarray(outcome(f, Gs, Ps, axis=ax)[0]).ravel() for f in (R.TP, R.FP, R.FN, R.TN)]
-            got = orc.confusion_counts_axis(G, P, axis=ax)
-            for a, b in zip(got, want):
-                np.testing.assert_array_equal(np.asarray(a).ravel(), b)
+            for f in ("TP", "FP", "FN", "TN"):
+                rec[f"met/{t}/{ax}/{f}"] = np.asarray(outcome(getattr(R, f), Gs, Ps, axis=ax)[0]).ravel().astype(np.float64)
             for w_fp in (0.5, 0.2):
                 (cs, _, e1) = outcome(R.coverage_score, gt=Gs, pd=Ps, w_fp=w_fp, axis=ax)
                 (we, _, e2) = outcome(R.weighted_error, gt=Gs, pd=Ps, w_fp=w_fp, axis=ax)
                 assert e1 is None and e2 is None
-                np.testing.assert_allclose(np.asarray(cs, float).ravel(), np.asarray(orc.coverage_score(G, P, w_fp=w_fp, axis=ax), float).ravel(), rtol=1e-14)
-                np.testing.assert_allclose(np.asarray(we, float).ravel(), np.asarray(orc.weighted_error(G, P, w_fp=w_fp, axis=ax), float).ravel(), rtol=1e-14)
+                rec[f"met/{t}/{ax}/{w_fp}/coverage"] = np.asarray(cs, float).ravel()
+                rec[f"met/{t}/{ax}/{w_fp}/weighted_error"] = np.asarray(we, float).ravel()
         (dl, _, e3) = outcome(R.description_length, gt=Gs, U=csr_matrix(Ub), V=csr_matrix(Vb), w_model=0.7, w_fp=2.0, w_fn=3.0)
-        assert e3 is None and float(dl) == pytest.approx(orc.description_length(G, Ub, Vb, w_model=0.7, w_fp=2.0, w_fn=3.0), rel=1e-14)
-        names = ["TP", "FP", "TN", "FN", "Recall", "Precision", "Accuracy", "F1", "RMSE", "MAE"]
-        (vals, _, e4) = outcome(R.get_metrics, gt=Gs, pd=Ps, metrics=names)
+        assert e3 is None
+        rec[f"met/{t}/description_length"] = float(dl)
+        (vals, _, e4) = outcome(R.get_metrics, gt=Gs, pd=Ps, metrics=METRIC_NAMES)
         assert e4 is None
+        rec[f"met/{t}/metrics"] = np.array(vals, float)
+
+
+def test_oracle_metrics_against_the_reference(ref):
+    import oracle as orc
+    for t, G, Ub, Vb, U, V, u, v in metric_cases():
+        np.testing.assert_array_equal(ref[f"met/{t}/prediction"], orc.boolean_product(U, V, u, v))
+        P = orc.boolean_product(Ub, Vb)
+        for ax in (None, 0, 1):
+            want = [ref[f"met/{t}/{ax}/{f}"] for f in ("TP", "FP", "FN", "TN")]
+            got = orc.confusion_counts_axis(G, P, axis=ax)
+            for a, b in zip(got, want):
+                np.testing.assert_array_equal(np.asarray(a).ravel(), b)
+            for w_fp in (0.5, 0.2):
+                np.testing.assert_allclose(ref[f"met/{t}/{ax}/{w_fp}/coverage"],
+                                           np.asarray(orc.coverage_score(G, P, w_fp=w_fp, axis=ax), float).ravel(), rtol=1e-14)
+                np.testing.assert_allclose(ref[f"met/{t}/{ax}/{w_fp}/weighted_error"],
+                                           np.asarray(orc.weighted_error(G, P, w_fp=w_fp, axis=ax), float).ravel(), rtol=1e-14)
+        assert ref[f"met/{t}/description_length"] == pytest.approx(orc.description_length(G, Ub, Vb, w_model=0.7, w_fp=2.0, w_fn=3.0), rel=1e-14)
         tp, fp, fn, tn = orc.confusion_counts(G, P)
         rmse, mae = orc.rmse_mae(G, P)
         mine = [tp, fp, tn, fn, *orc.boolean_scores(tp, fp, fn, tn), rmse, mae]
-        np.testing.assert_allclose(np.array(vals, float), np.array(mine, float), rtol=1e-14)
+        np.testing.assert_allclose(ref[f"met/{t}/metrics"], np.array(mine, float), rtol=1e-14)
+
+
+RECORDERS = (record_generator, record_line_search, record_stopping_rule, record_container_helpers, record_penalty_fit, record_wnmf_fits,
+             record_pnlpf_and_threshold, record_entry_scores, record_metrics)
