@@ -920,7 +920,8 @@ int bmf_cover_count_wide(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, i
                          const uint64_t* rowbitsB, const uint32_t* colbitsA, const uint32_t* colbitsB, int64_t ldcb,
                          unsigned long long* counts, void* stream);
 /* sums[0] += sum |X - U V^T|, sums[1] += sum (X - U V^T)^2 over all cells, U = [UA | UB], V = [VA | VB] (fp32 shadows, rows_pad x 64
- * each, zero padded), one fp16 product per cell (utils/metrics.py:149-160).  XTbits: the transposed bit matrix, or its bmf_tile_bits
+ * each, zero padded) (utils/metrics.py:149-160): below 2^24 padded cells (m_pad n_pad) exact products summed in fp64, from 2^24 cells up
+ * one fp16 product per cell (its ~2e-4 |P| per cell averages out in the sum).  XTbits: the transposed bit matrix, or its bmf_tile_bits
  * copy with x_tiled = 1.  ws: (m_pad + n_pad) * 128 uint16.  m_pad % 256 == 0, n_pad % 64 == 0. */
 int bmf_resid_sums_wide(const uint32_t* XTbits, int64_t ldxt, int64_t m_pad, int64_t n_pad, const float* UA, const float* UB,
                         const float* VA, const float* VB, uint16_t* ws, double* sums, int x_tiled, void* stream);

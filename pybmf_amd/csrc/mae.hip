@@ -666,10 +666,67 @@ __global__ __launch_bounds__(256) void to_f16_wide_kernel(const float* __restric
     }
 }
 
+// sums[0] += sum |X - U V^T|, sums[1] += sum (X - U V^T)^2 below 2^24 cells, where one fp16 product per cell (~2e-4 |P|) does not
+// average out: exact products of the fp32 shadows summed in fp64.  A workgroup takes a 64 x 64 tile of cells, 16 per thread (rows
+// ty + 16 a, columns tx + 16 b), both 64-column blocks staged in LDS one after the other.  X^T: plain rows, or the bmf_tile_bits
+// copy (block (j / 256, word / 16) = 256 rows x 16 words, contiguous; see mae32_kernel).  Padded rows / columns are zero in U, V and
+// X.  Not tuned: a correctness row at sizes where the pass is short.
+template <bool XTILED>
+__global__ __launch_bounds__(256) void resid_wide_f64_kernel(const uint32_t* __restrict__ XT, int64_t ldxt, const float* __restrict__ UA,
+                                                              const float* __restrict__ UB, const float* __restrict__ VA,
+                                                              const float* __restrict__ VB, double* __restrict__ sums) {
+    __shared__ float us[64][65], vs[64][65];
+    __shared__ double red[2][4];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lane = tid & 63, wave = tid >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * 64, j0 = (int64_t)blockIdx.y * 64;
+    double p[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) p[a][b] = 0.0;
+    for (int blk = 0; blk < 2; ++blk) {
+        const float* U = blk ? UB : UA;
+        const float* V = blk ? VB : VA;
+        __syncthreads();
+        for (int e = tid; e < 64 * 64; e += 256) {
+            const int r = e >> 6, c = e & 63;
+            us[r][c] = U[(i0 + r) * 64 + c];
+            vs[r][c] = V[(j0 + r) * 64 + c];
+        }
+        __syncthreads();
+        for (int c = 0; c < 64; ++c) {
+            double u[4], v[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) { u[a] = (double)us[ty + 16 * a][c]; v[a] = (double)vs[tx + 16 * a][c]; }
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) p[a][b] = fma(u[a], v[b], p[a][b]);
+        }
+    }
+    double s_abs = 0.0, s_sq = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int64_t i = i0 + ty + 16 * a, j = j0 + tx + 16 * b, w = i >> 5;
+            const int64_t idx = XTILED ? ((((j >> 8) * (ldxt >> 4) + (w >> 4)) * 256 + (j & 255)) * 16 + (w & 15)) : j * ldxt + w;
+            const double r = (double)((XT[idx] >> (i & 31)) & 1u) - p[a][b];
+            s_abs += fabs(r);
+            s_sq += r * r;
+        }
+    s_abs = wave_sum(s_abs);
+    s_sq = wave_sum(s_sq);
+    if (lane == 0) { red[0][wave] = s_abs; red[1][wave] = s_sq; }
+    __syncthreads();
+    if (tid < 2) atomicAdd(sums + tid, (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]));
+}
+
 }  // namespace
 
-// sums[0] += sum |X - U V^T|, sums[1] += sum (X - U V^T)^2 for factors of two 64-column blocks each (64 < k <= 128): the single-product
-// fp16 pass at K = 128.  ws: (m_pad + n_pad) * 128 uint16.
+// sums[0] += sum |X - U V^T|, sums[1] += sum (X - U V^T)^2 for factors of two 64-column blocks each (64 < k <= 128).  By size, as
+// bmf_mae_launch: the single-product fp16 pass at K = 128 from 2^24 padded cells up (the per-cell error averages out over the sum),
+// resid_wide_f64_kernel below that (ws unused).  ws: (m_pad + n_pad) * 128 uint16.
 int bmf_mae_wide_launch(const uint32_t* XT, int64_t ldxt, int64_t m_pad, int64_t n_pad, const float* UA, const float* UB, const float* VA,
                         const float* VB, uint16_t* ws, double* sums, int x_tiled, hipStream_t s) {
     BMF_REQUIRE(XT && UA && UB && VA && VB && ws && sums, "bmf_resid_sums_wide: null pointer");
@@ -678,6 +735,13 @@ int bmf_mae_wide_launch(const uint32_t* XT, int64_t ldxt, int64_t m_pad, int64_t
     BMF_REQUIRE(!x_tiled || (n_pad % 256 == 0 && ldxt % 16 == 0 && ldxt * 32 == m_pad), "bmf_resid_sums_wide: the tiled X^T needs n_pad %% 256 == 0 and ldxt == m_pad / 32, a multiple of 16");
     BMF_REQUIRE(bmf_aligned16(XT) && bmf_aligned16(UA) && bmf_aligned16(UB) && bmf_aligned16(VA) && bmf_aligned16(VB) && bmf_aligned16(ws),
                 "bmf_resid_sums_wide: alignment");
+    if (m_pad * n_pad < (int64_t(1) << 24)) {
+        const dim3 grid((unsigned)(m_pad / 64), (unsigned)(n_pad / 64));
+        if (x_tiled) BMF_LAUNCH(resid_wide_f64_kernel<true>, grid, dim3(256), 0, s, XT, ldxt, UA, UB, VA, VB, sums);
+        else BMF_LAUNCH(resid_wide_f64_kernel<false>, grid, dim3(256), 0, s, XT, ldxt, UA, UB, VA, VB, sums);
+        BMF_LAUNCH_CHECK();
+        return BMF_OK;
+    }
     uint16_t* Uh = ws;
     uint16_t* Vh = ws + m_pad * 128;
     auto blocks = [](int64_t rows) { const int64_t b = (rows * 32 + 255) / 256; return (unsigned)(b < 2048 ? b : 2048); };

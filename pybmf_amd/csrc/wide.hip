@@ -8,8 +8,8 @@
 //                          (:142,157; WNMF.py:99,106) -- one 64 x 64 block of the Gram matrix per call, accumulating;
 //   * bmf_gram_cross:      G[a][b] = F_a^T F_b (partial sums per row range, summed by bmf_reduce_slabs);
 //   * bmf_cover_count_wide: TP / FP of the Boolean product over all 128 factors (utils/common.py:110-151, metrics.py:56-68);
-//   * bmf_resid_sums_wide: sum |X - U V^T| and sum (X - U V^T)^2 with the product over all 128 columns (metrics.py:149-160) on
-//                          the fp16 MFMA kernel of mae.hip instantiated at K = 128.
+//   * bmf_resid_sums_wide: sum |X - U V^T| and sum (X - U V^T)^2 with the product over all 128 columns (metrics.py:149-160):
+//                          exact products in fp64 below 2^24 cells, from 2^24 cells up the fp16 MFMA kernel of mae.hip at K = 128.
 // These are correctness rows (SURVEY 8f has no configuration with k > 64): simple tilings, no tuning.
 #include "common.h"
 

@@ -537,7 +537,7 @@ class ContinuousModel(BaseModel):
         from .._lib import lib, check, ptr
         from ..engine import _stream, round_up
         B = self._bits
-        if self.k > L.MAX_KP:   # two 64-column blocks per factor, one fp16 product per cell (bmf_resid_sums_wide)
+        if self.k > L.MAX_KP:   # two 64-column blocks per factor (bmf_resid_sums_wide)
             from ..wide import BK
             lo, hi = getattr(self, "_rows", (0, self.m))
             with torch.cuda.device(B.device):

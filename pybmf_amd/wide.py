@@ -237,7 +237,7 @@ class WideMUEngine:
         return rec + rg, rec, rg, rmse, mae, (tp, fp, fn, self.m * self.n - tp - fp - fn)
 
     def residual_sums(self):
-        """(sum |X - U V^T|, sum (X - U V^T)^2) of the current factors by the direct pass (one fp16 product per cell)."""
+        """(sum |X - U V^T|, sum (X - U V^T)^2) of the current factors by the direct pass (bmf_resid_sums_wide)."""
         X = self.X
         with torch.cuda.device(self.device):
             if self._mae_ws is None:
