@@ -51,6 +51,36 @@ import contextlib  # noqa: E402
 _NULL_CTX = contextlib.nullcontext()
 
 
+class HostRows:
+    """The log rows of a pipelined loop (iteration t + 1 enqueued before the scalars of t are read): LOG_ROWS pinned rows of eight fp64
+    scalars, each with the event that completes it.  Row `it` lives in slot it % LOG_ROWS until a later iteration takes the slot."""
+    LOG_ROWS = 8
+
+    def __init__(self):
+        self.host = torch.zeros((self.LOG_ROWS, 8), dtype=torch.float64).pin_memory()
+        self._events = [None] * self.LOG_ROWS
+
+    def slot(self, it: int) -> torch.Tensor:
+        return self.host[it % self.LOG_ROWS]
+
+    def mark(self, it: int):
+        """Row `it` is complete once the work enqueued so far on the current stream is."""
+        ev = torch.cuda.Event()
+        ev.record()
+        self._events[it % self.LOG_ROWS] = (it, ev)
+
+    def has(self, it: int) -> bool:
+        e = self._events[it % self.LOG_ROWS]
+        return e is not None and e[0] == it
+
+    def wait(self, it: int) -> np.ndarray:
+        """A host copy of row `it` (an event wait, no polling)."""
+        if not self.has(it):
+            raise RuntimeError(f"row {it} is not available")
+        self._events[it % self.LOG_ROWS][1].synchronize()
+        return self.slot(it).numpy().copy()
+
+
 def require_gpu(device) -> torch.device:
     device = torch.device(device)
     if device.type != "cuda" or not torch.cuda.is_available():
@@ -1213,13 +1243,9 @@ class MaskedMUEngine:
         check(lib.bmf_mu_epilogue(C.byref(a), _stream()), "bmf_mu_epilogue")
 
     # ---- whole iterations enqueued by one C call each (bmf_masked_iterate), scalars read one iteration late ---------------------
-    LOG_ROWS = 8
-
     def can_pipeline(self):
         """One rank, no link or the sigmoid link (the Kullback-Leibler denominator is made with torch ops between the kernels)."""
-        import os
-        return (not self.sharded and self.link in (0, L.LINK_SIGMOID) and not self.real_counts and not (self.link and self.real is not None)
-                and os.environ.get("BMF_MASKED_PIPELINE", "1") != "0")   # (A/B switch)
+        return not self.sharded and self.link in (0, L.LINK_SIGMOID) and not self.real_counts and not (self.link and self.real is not None)
 
     def _side_args(self, ls, rows):
         if ls.get("part") is None:
@@ -1250,8 +1276,7 @@ class MaskedMUEngine:
         st.sums2, st.counts, st.nbU, st.nbV = self.sums2.data_ptr(), self.counts.data_ptr(), self.partU.shape[0], self.partV.shape[0]
         self.sums2.zero_()
         self.counts.zero_()
-        self._rows_host = torch.zeros((self.LOG_ROWS, 8), dtype=torch.float64).pin_memory()
-        self._events = [None] * self.LOG_ROWS
+        self._ring = HostRows()
         self._loop = st
         return st
 
@@ -1259,21 +1284,14 @@ class MaskedMUEngine:
         """Enqueue iteration `it` (update = False: only the scalars of the current state, log row 0); ``row(it, reg)`` waits for its row.
         At most LOG_ROWS - 1 iterations may be outstanding."""
         st = self._loop_state()
-        slot = it % self.LOG_ROWS
         with torch.cuda.device(self.device):
-            check(lib.bmf_masked_iterate(C.byref(st), float(reg), int(bool(update)), C.c_void_p(self._rows_host[slot].data_ptr()), _stream()),
+            check(lib.bmf_masked_iterate(C.byref(st), float(reg), int(bool(update)), C.c_void_p(self._ring.slot(it).data_ptr()), _stream()),
                   "bmf_masked_iterate")
-            ev = torch.cuda.Event()
-            ev.record()
-        self._events[slot] = (it, ev)
+            self._ring.mark(it)
 
     def row(self, it: int, reg: float):
-        """The scalars of iteration `it` as ``scalars(reg)`` returns them (an event wait, no polling)."""
-        slot = it % self.LOG_ROWS
-        if self._events[slot] is None or self._events[slot][0] != it:
-            raise RuntimeError(f"row {it} is not available")
-        self._events[slot][1].synchronize()
-        h = self._rows_host[slot].numpy().copy()
+        """The scalars of iteration `it` as ``scalars(reg)`` returns them."""
+        h = self._ring.wait(it)
         return self._decode_scalars(h, reg, self.bits is not None or self.real is not None, float(self.m_total) * float(self.n))
 
     def previous_factors(self):
@@ -1534,11 +1552,9 @@ class LinkMUEngine:
         check(lib.bmf_mu_epilogue(C.byref(a), _stream()), "bmf_mu_epilogue")
 
     # ---- whole iterations enqueued by one C call each (bmf_link_iterate), scalars read one iteration late -----------------------
-    LOG_ROWS = 8
-
     def can_pipeline(self):
         """One rank, the 16-bit MFMA flavour."""
-        return not self.sharded and self.mfma == "bf16" and os.environ.get("BMF_LINK_PIPELINE", "1") != "0"   # (A/B switch)
+        return not self.sharded and self.mfma == "bf16"
 
     def _loop_state(self):
         if getattr(self, "_loop", None) is not None:
@@ -1559,34 +1575,24 @@ class LinkMUEngine:
         if self.obs_bits is not None:
             st.Obits = self.obs_bits.bits.data_ptr()
         st.nbU, st.nbV = self.partU.shape[0], self.partV.shape[0]
-        self._rows_host = torch.zeros((self.LOG_ROWS, 8), dtype=torch.float64).pin_memory()
-        self._events = [None] * self.LOG_ROWS
+        self._ring = HostRows()
         self._loop = st
         return st
 
     def iterate(self, it: int, reg: float, update: bool = True):
         """Enqueue iteration `it` (update = False: only the scalars of the current state, log row 0); ``row(it, reg)`` waits for its row."""
         st = self._loop_state()
-        slot = it % self.LOG_ROWS
         with torch.cuda.device(self.device):
-            check(lib.bmf_link_iterate(C.byref(st), float(reg), int(bool(update)), C.c_void_p(self._rows_host[slot].data_ptr()), _stream()),
+            check(lib.bmf_link_iterate(C.byref(st), float(reg), int(bool(update)), C.c_void_p(self._ring.slot(it).data_ptr()), _stream()),
                   "bmf_link_iterate")
-            ev = torch.cuda.Event()
-            ev.record()
-        self._events[slot] = (it, ev)
+            self._ring.mark(it)
 
     def row(self, it: int, reg: float):
-        """The scalars of iteration `it` as ``scalars(reg)`` returns them (an event wait, no polling)."""
-        slot = it % self.LOG_ROWS
-        if self._events[slot] is None or self._events[slot][0] != it:
-            raise RuntimeError(f"row {it} is not available")
-        self._events[slot][1].synchronize()
-        h = self._rows_host[slot].numpy().copy()
+        """The scalars of iteration `it` as ``scalars(reg)`` returns them."""
+        h = self._ring.wait(it)
         return self._decode(s=(h[3], h[4], h[0]), tp=int(h[5]), fp=int(h[6]), pu=float(h[1]), pv=float(h[2]), reg=reg)
 
-    def previous_factors(self):
-        """The iterate before the last enqueued update: what a loop that ran one iteration past its stopping rule returns."""
-        return self.Up64[: self.m, : self.k].cpu().numpy(), self.Vp64[: self.n, : self.k].cpu().numpy()
+    previous_factors = MaskedMUEngine.previous_factors   # (the same Up64 / Vp64 snapshot, written by bmf_link_iterate)
 
     def _decode(self, s, tp, fp, pu, pv, reg):
         cells = float(self.m_total) * float(self.n)

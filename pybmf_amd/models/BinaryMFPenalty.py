@@ -14,7 +14,7 @@ import numpy as np
 
 from .. import _lib as L
 from ..utils import header, record_many, scores_from_counts
-from .ContinuousModel import ContinuousModel
+from .ContinuousModel import ContinuousModel, mu_loop
 
 
 LOG_SUM_GT, LOG_SUM_PD = 14, 15   # spare columns of a log row (L.LOG_COLS = 16): sum gt, sum pd of a real-valued training matrix
@@ -108,13 +108,14 @@ class BinaryMFPenalty(ContinuousModel):
         eng.load_factors(self.U[lo:hi], self.V)
         eng.prepare()
         rows = []
+        # X_val / X_test, and the training entries under task='prediction': scored every iteration like the training matrix
+        # (BinaryMFPenalty.py:71,97 -> BaseModel.evaluate :209-257)
         extras = [] if self._scorers else None
-        n_iter = 0
 
-        def log_row(it, reg):
-            err, rec, rg, rmse, mae, cnt = eng.scalars(reg)
+        def on_row(it, reg, scalars):
+            err, rec, rg, rmse, mae, cnt = scalars
             if extras is not None:
-                extras.append(self._engine_scores(eng))
+                extras.append(self._engine_scores(eng, **self._scorer_link()))
             r = np.zeros(L.LOG_COLS)
             r[[L.LOG_ITER, L.LOG_ERROR, L.LOG_REC, L.LOG_REG, L.LOG_REGERR, L.LOG_RMSE, L.LOG_MAE]] = it, err, rec, reg, rg, rmse, mae
             r[L.LOG_TP:L.LOG_TN + 1] = cnt[:4]
@@ -122,52 +123,17 @@ class BinaryMFPenalty(ContinuousModel):
                 r[LOG_SUM_GT], r[LOG_SUM_PD] = cnt[4], cnt[5]
             rows.append(r)
             return rg
-        if extras is None and getattr(eng, "can_pipeline", lambda: False)():
-            # Whole iterations enqueued by one C call each (bmf_masked_iterate); iteration t + 1 is enqueued BEFORE the scalars of t are
-            # read, so the device never waits for the host.  The loop runs one iteration past its stopping rule; the engine keeps the
-            # iterate before (the regulariser schedule does not depend on the scalars).  Same rows, same decisions.
-            def row(it, reg, h):
-                err, rec, rg, rmse, mae, cnt = h
-                r = np.zeros(L.LOG_COLS)
-                r[[L.LOG_ITER, L.LOG_ERROR, L.LOG_REC, L.LOG_REG, L.LOG_REGERR, L.LOG_RMSE, L.LOG_MAE]] = it, err, rec, reg, rg, rmse, mae
-                r[L.LOG_TP:L.LOG_TN + 1] = cnt
-                rows.append(r)
-                return rg
-            reg = float(self.reg)
-            eng.iterate(0, reg, update=False)
-            eng.iterate(1, reg)
-            rg_old = row(0, reg, eng.row(0, reg))
-            while True:
-                n_iter += 1
-                reg_next = min(reg * self.reg_growth, self.max_reg)
-                eng.iterate(n_iter + 1, reg_next)
-                rg = row(n_iter, reg, eng.row(n_iter, reg))
-                diff = abs(rg_old - rg)
-                rg_old = rg
-                improving = self.early_stop(error=rg_old, diff=diff, n_iter=n_iter, verbose=False)
-                self.reg = reg_next
-                if not improving:
-                    break
-                reg = reg_next
-            U_local, self.V = eng.previous_factors()
-            eng.load_factors(U_local, self.V)
-        else:
-            rg_old = log_row(0, float(self.reg))
-            improving = True
-            while improving:
-                n_iter += 1
-                eng.update(float(self.reg))
-                rg = log_row(n_iter, float(self.reg))
-                diff = abs(rg_old - rg)
-                rg_old = rg
-                improving = self.early_stop(error=rg_old, diff=diff, n_iter=n_iter, verbose=False)
-                self.reg = min(self.reg * self.reg_growth, self.max_reg)
-            U_local, self.V = eng.factors()
+        n_iter, self.reg, (U_local, self.V) = mu_loop(eng, self.reg, on_row, self.early_stop, growth=self.reg_growth, max_reg=self.max_reg,
+                                                      scored=extras is not None)
         self.U = self._gather_rows(U_local)
         log = np.array(rows)
         self._log_to_frames(log, extras)
         self.early_stop(error=float(log[-1, L.LOG_REGERR]), diff=self._last_diff, n_iter=n_iter)
         self.n_iter = n_iter
+
+    def _scorer_link(self):
+        """Link arguments of the scorers of the extra data sets (PNLPF: its sigmoid-link prediction)."""
+        return {}
 
     def _stop_reason(self, last, n_iter):
         self.early_stop(error=float(last[L.LOG_REGERR]), diff=self._last_diff, n_iter=n_iter)

@@ -591,6 +591,46 @@ class _PadDims:
         self.m_pad, self.n_pad = round_up(max(self.m, 1), L.ROW_PAD), round_up(self.n, L.ROW_PAD)
 
 
+def mu_loop(eng, reg, on_row, early_stop, growth=1.0, max_reg=np.inf, scored=False):
+    """The loop of the multiplicative-update models on an engine with the prepare / update / scalars protocol (prepared, factors
+    loaded).  Update t uses `reg`, grown as min(reg * growth, max_reg) after each update.  ``on_row(it, reg, scalars)`` records log
+    row `it` (and scores the extra data sets, `scored`) and returns the value the stopping rule sees; ``early_stop`` is the model's.
+    Returns (n_iter, `reg` one growth step past the last update, (U_local, V)).
+
+    Without extra data sets and on an engine that can (``eng.can_pipeline()``), whole iterations are enqueued by one C call each and
+    iteration t + 1 is enqueued BEFORE the scalars of t are read, so the device never waits for the host.  The loop then runs one
+    iteration past its stopping rule and returns the iterate before (the regulariser schedule does not depend on the scalars): same
+    rows, same decisions, same factors as the stepwise loop."""
+    grow = lambda r: min(r * growth, max_reg)  # noqa: E731
+    n_iter = 0
+    if not scored and eng.can_pipeline():
+        eng.iterate(0, float(reg), update=False)
+        eng.iterate(1, float(reg))
+        old = on_row(0, float(reg), eng.row(0, float(reg)))
+        while True:
+            n_iter += 1
+            reg_next = grow(reg)
+            eng.iterate(n_iter + 1, float(reg_next))
+            new = on_row(n_iter, float(reg), eng.row(n_iter, float(reg)))
+            diff, old = abs(old - new), new
+            reg = reg_next
+            if not early_stop(error=old, diff=diff, n_iter=n_iter, verbose=False):
+                break
+        factors = eng.previous_factors()
+        eng.load_factors(*factors)
+        return n_iter, reg, factors
+    old = on_row(0, float(reg), eng.scalars(float(reg)))
+    improving = True
+    while improving:
+        n_iter += 1
+        eng.update(float(reg))
+        new = on_row(n_iter, float(reg), eng.scalars(float(reg)))
+        diff, old = abs(old - new), new
+        improving = early_stop(error=old, diff=diff, n_iter=n_iter, verbose=False)
+        reg = grow(reg)
+    return n_iter, reg, eng.factors()
+
+
 def unique_values_mapping(arr):
     """Map every value to (its rank among the distinct values) / (number of distinct values), i.e. onto an arithmetic
     sequence in [0, 1) (PyBMF/models/ContinuousModel.py:225-231)."""

@@ -15,8 +15,6 @@ the Boolean scores of the factors thresholded at 0.5.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
 from .. import _lib as L
@@ -79,7 +77,7 @@ class ELBMF(ContinuousModel):
             return self.early_stop(error=gap, diff=abs(gap - gap_last), n_iter=n_iter)
 
         n_iter = 0
-        if obs is None and extras is None and os.environ.get("BMF_PALM_LOOP", "c") != "python":
+        if extras is None and eng.can_pipeline():
             # One C call per iteration (bmf_palm_iterate), and iteration t + 1 is enqueued BEFORE the host reads the scalars of t: the
             # device never waits for the stopping rule.  When the rule fires at t, t + 1 has already run -- its `previous iterate`
             # (what ELBMF calls U_last, :124) is the factor pair of t, which is what the loop returns.

@@ -4,7 +4,7 @@ Drop-in for ``PyBMF.models.PNLPF`` (``PyBMF/models/PNLPF.py``):
 
     min 1/2 ||X - sigmoid(link_lamda (U V^T - 1/2))||_F^2 + 1/2 reg ||U^2 - U||_F^2 + 1/2 reg ||V^2 - V||_F^2
 
-The loop is the inherited ``BinaryMFPenalty._fit`` (BinaryMFPenalty.py:61-115); the two updates (:61-91) cannot be
+The loop is the inherited ``BinaryMFPenalty._fit_masked`` (BinaryMFPenalty.py:61-115); the two updates (:61-91) cannot be
 re-associated, so each is one tile-fused pass over X (csrc/link.hip, ``bmf_link_pass``) followed by the shared fp64
 epilogue.  Under a mask / weight matrix the contractions run over the observed cells instead (csrc/masked.hip,
 ``bmf_masked_link_pass``).
@@ -41,74 +41,11 @@ class PNLPF(BinaryMFPenalty):
     def _fit(self):
         if getattr(self, "task", None) is None:
             raise AttributeError(f"'{type(self).__name__}' object has no attribute 'task'")
-        eng = self._eng = self._link_engine()
-        lo, hi = self._rows
-        eng.load_factors(self.U[lo:hi], self.V)
-        eng.prepare()
-        rows = []
-        n_iter = 0
-        # X_val / X_test, and the training entries under task='prediction': scored every iteration like the training matrix (the
-        # inherited loop, BinaryMFPenalty.py:71,97 -> BaseModel.evaluate :209-257), RMSE / MAE against the LINK prediction (:51-58)
-        extras = [] if self._scorers else None
+        self._fit_masked(self._link_engine())
 
-        def log_row(it, reg):
-            err, rec, rg, rmse, mae, cnt = eng.scalars(reg)
-            if extras is not None:
-                extras.append(self._engine_scores(eng, link=L.LINK_SIGMOID, lamda=float(self.link_lamda)))
-            r = np.zeros(L.LOG_COLS)
-            r[[L.LOG_ITER, L.LOG_ERROR, L.LOG_REC, L.LOG_REG, L.LOG_REGERR, L.LOG_RMSE, L.LOG_MAE]] = it, err, rec, reg, rg, rmse, mae
-            r[L.LOG_TP:L.LOG_TN + 1] = cnt[:4]
-            if len(cnt) == 6:
-                from .BinaryMFPenalty import LOG_SUM_GT, LOG_SUM_PD
-                r[LOG_SUM_GT], r[LOG_SUM_PD] = cnt[4], cnt[5]
-            rows.append(r)
-            return rg
-        if extras is None and eng.can_pipeline():
-            # Whole iterations enqueued by one C call each (bmf_link_iterate); iteration t + 1 is enqueued BEFORE the scalars of t are
-            # read, so the device never waits for the host (BinaryMFPenalty._fit_masked has the same loop on the masked kernels).  The
-            # loop runs one iteration past its stopping rule; the engine keeps the iterate before.  Same rows, same decisions.
-            def row(it, reg, h):
-                err, rec, rg, rmse, mae, cnt = h
-                r = np.zeros(L.LOG_COLS)
-                r[[L.LOG_ITER, L.LOG_ERROR, L.LOG_REC, L.LOG_REG, L.LOG_REGERR, L.LOG_RMSE, L.LOG_MAE]] = it, err, rec, reg, rg, rmse, mae
-                r[L.LOG_TP:L.LOG_TN + 1] = cnt
-                rows.append(r)
-                return rg
-            reg = float(self.reg)
-            eng.iterate(0, reg, update=False)
-            eng.iterate(1, reg)
-            rg_old = row(0, reg, eng.row(0, reg))
-            while True:
-                n_iter += 1
-                reg_next = min(reg * self.reg_growth, self.max_reg)
-                eng.iterate(n_iter + 1, reg_next)
-                rg = row(n_iter, reg, eng.row(n_iter, reg))
-                diff = abs(rg_old - rg)
-                rg_old = rg
-                improving = self.early_stop(error=rg_old, diff=diff, n_iter=n_iter, verbose=False)
-                self.reg = reg_next
-                if not improving:
-                    break
-                reg = reg_next
-            U_local, self.V = eng.previous_factors()
-            eng.load_factors(U_local, self.V)
-        else:
-            rg_old = log_row(0, float(self.reg))
-            improving = True
-            while improving:
-                n_iter += 1
-                eng.update(float(self.reg))
-                rg = log_row(n_iter, float(self.reg))
-                diff = abs(rg_old - rg)
-                rg_old = rg
-                improving = self.early_stop(error=rg_old, diff=diff, n_iter=n_iter, verbose=False)
-                self.reg = min(self.reg * self.reg_growth, self.max_reg)
-            U_local, self.V = eng.factors()
-        self.U = self._gather_rows(U_local)
-        log = np.array(rows)
-        self._log_to_frames(log, extras)
-        self.early_stop(error=float(log[-1, L.LOG_REGERR]), diff=self._last_diff, n_iter=n_iter)
-        self.n_iter = n_iter
+    def _scorer_link(self):
+        # X_val / X_test (and the training entries under task='prediction'): RMSE / MAE against the LINK prediction (PNLPF.py:51-58)
+        return dict(link=L.LINK_SIGMOID, lamda=float(self.link_lamda))
 
     def get_prediction(self):
         return get_prediction_with_sigmoid(U=self.U, V=self.V, link_lamda=self.link_lamda)

@@ -19,7 +19,7 @@ import numpy as np
 
 from .. import _lib as L
 from ..utils import header, record_many
-from .ContinuousModel import ContinuousModel
+from .ContinuousModel import ContinuousModel, mu_loop
 
 
 class WNMF(ContinuousModel):
@@ -178,7 +178,7 @@ class WNMF(ContinuousModel):
 
     def _fit_masked(self, eng=None):
         """W = 'mask' (stored pattern) or weights: contractions over the observed cells (bmf_masked_pass).  `eng`: another engine with
-        the prepare / update / scalars protocol (the two-block engine of a rank above 64)."""
+        the prepare / update / scalars protocol (the two-block engine of a rank above 64, the Kullback-Leibler engines)."""
         from ..engine import MaskedMUEngine
         if eng is None:
             eng = MaskedMUEngine(self._obs, self.k, L.MODE_WNMF, bits=self._bits if self._boolean else None,
@@ -189,40 +189,13 @@ class WNMF(ContinuousModel):
         eng.load_factors(self.U[lo:hi], self.V)
         eng.prepare()
         rows = []
-        n_iter = 0
-        if not self._scorers and getattr(eng, "can_pipeline", lambda: False)():
-            # one C call per iteration, iteration t + 1 enqueued before the scalars of t are read (see BinaryMFPenalty._fit_masked)
-            eng.iterate(0, 0.0, update=False)
-            eng.iterate(1, 0.0)
-            err_old, _, _, rmse, mae, _ = eng.row(0, 0.0)
-            rows.append((n_iter, err_old, rmse, mae))
-            while True:
-                n_iter += 1
-                eng.iterate(n_iter + 1, 0.0)
-                err, _, _, rmse, mae, _ = eng.row(n_iter, 0.0)
-                diff = abs(err_old - err)
-                err_old = err
-                rows.append((n_iter, err, rmse, mae))
-                if not self.early_stop(error=err_old, diff=diff, n_iter=n_iter, verbose=False):
-                    break
-            U_local, self.V = eng.previous_factors()
-            eng.load_factors(U_local, self.V)
-            self.U = self._gather_rows(U_local)
-            return rows
-        err_old, _, _, rmse, mae, _ = eng.scalars(0.0)
-        rows.append((n_iter, err_old, rmse, mae))
-        self._note(eng)
-        improving = True
-        while improving:
-            n_iter += 1
-            eng.update(0.0)
-            err, _, _, rmse, mae, _ = eng.scalars(0.0)
+
+        def on_row(it, reg, scalars):
+            err, _, _, rmse, mae, _ = scalars
+            rows.append((it, err, rmse, mae))
             self._note(eng)
-            diff = abs(err_old - err)
-            err_old = err
-            rows.append((n_iter, err, rmse, mae))
-            improving = self.early_stop(error=err_old, diff=diff, n_iter=n_iter, verbose=False)
-        U_local, self.V = eng.factors()
+            return err
+        _, _, (U_local, self.V) = mu_loop(eng, 0.0, on_row, self.early_stop, scored=bool(self._scorers))
         self.U = self._gather_rows(U_local)
         return rows
 
@@ -254,48 +227,7 @@ class WNMF(ContinuousModel):
             pattern = csr_matrix((np.ones(Xs.nnz, dtype=np.uint8), Xs.indices, Xs.indptr), shape=Xs.shape)
             lo, hi = self._rows
             obs_bits = BitMatrix(pattern, self.device, row_lo=lo, row_hi=hi)
-        eng = self._eng = LinkMUEngine(self._bits, self.k, L.LINK_KL, L.MODE_WNMF, obs_bits=obs_bits, sharded=self._sharded)
-        lo, hi = self._rows
-        eng.load_factors(self.U[lo:hi], self.V)
-        eng.prepare()
-        rows = []
-        n_iter = 0
-        if not self._scorers and eng.can_pipeline():
-            # one C call per iteration (bmf_link_iterate), iteration t + 1 enqueued before the scalars of t are read (see
-            # BinaryMFPenalty._fit_masked): the loop overshoots its stopping rule by one iteration and returns the iterate before
-            eng.iterate(0, 0.0, update=False)
-            eng.iterate(1, 0.0)
-            err_old, _, _, rmse, mae, _ = eng.row(0, 0.0)
-            rows.append((n_iter, err_old, rmse, mae))
-            while True:
-                n_iter += 1
-                eng.iterate(n_iter + 1, 0.0)
-                err, _, _, rmse, mae, _ = eng.row(n_iter, 0.0)
-                diff = abs(err_old - err)
-                err_old = err
-                rows.append((n_iter, err, rmse, mae))
-                if not self.early_stop(error=err_old, diff=diff, n_iter=n_iter, verbose=False):
-                    break
-            U_local, self.V = eng.previous_factors()
-            eng.load_factors(U_local, self.V)
-            self.U = self._gather_rows(U_local)
-            return rows
-        err_old, _, _, rmse, mae, _ = eng.scalars(0.0)
-        rows.append((n_iter, err_old, rmse, mae))
-        self._note(eng)
-        improving = True
-        while improving:
-            n_iter += 1
-            eng.update(0.0)
-            err, _, _, rmse, mae, _ = eng.scalars(0.0)
-            self._note(eng)
-            diff = abs(err_old - err)
-            err_old = err
-            rows.append((n_iter, err, rmse, mae))
-            improving = self.early_stop(error=err_old, diff=diff, n_iter=n_iter, verbose=False)
-        U_local, self.V = eng.factors()
-        self.U = self._gather_rows(U_local)
-        return rows
+        return self._fit_masked(LinkMUEngine(self._bits, self.k, L.LINK_KL, L.MODE_WNMF, obs_bits=obs_bits, sharded=self._sharded))
 
     def _note(self, eng):
         """RMSE / MAE of the extra data sets (val / test; train under task='prediction') at the engine's current state."""

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as L
 from ._lib import lib, check, ptr
-from .engine import BitMatrix, _stream, xf_slots, xf_slots_i8
+from .engine import BitMatrix, HostRows, _stream, xf_slots, xf_slots_i8
 
 
 class PalmEngine:
@@ -74,8 +74,6 @@ class PalmEngine:
             self._grad_ready = {"U": False, "V": False}
 
     # ---- the ELBMF loop body as ONE C call per iteration (bmf_palm_iterate), and the scalars of an iteration read back late ----
-    LOG_ROWS = 8
-
     def _state(self):
         """bmf_palm_state over this engine's buffers (all-ones mask, int8 operands)."""
         if getattr(self, "_st", None) is not None:
@@ -84,20 +82,19 @@ class PalmEngine:
             raise NotImplementedError("bmf_palm_iterate / bmf_primp_iterate: the loops under the all-ones mask on the int8 operands")
         X, kp, dev = self.X, self.kp, self.device
         with torch.cuda.device(dev):   # the log rows are written by the scalars kernel straight into pinned host memory: no copy in the stream
-            self._log_host = torch.zeros((self.LOG_ROWS, 8), dtype=torch.float64).pin_memory()
+            self._ring = HostRows()
         st = L.PalmState()
         st.struct_bytes = C.sizeof(L.PalmState)
         st.m, st.n, st.k, st.kp, st.variant, st.norm_kind = X.m, X.n, self.k, kp, self.variant, self.norm_kind
-        st.splits_xv, st.splits_xtu, st.gram_blocks, st.dot_blocks, st.log_rows = self.splits_xv, self.splits_xtu, self.gram_blocks, self.dot_blocks, self.LOG_ROWS
+        st.splits_xv, st.splits_xtu, st.gram_blocks, st.dot_blocks, st.log_rows = self.splits_xv, self.splits_xtu, self.gram_blocks, self.dot_blocks, HostRows.LOG_ROWS
         st.m_pad, st.n_pad, st.Xbits, st.ldx = X.m_pad, X.n_pad, X.bits.data_ptr(), X.ldx
         st.Xtiled, st.XTtiled = self._tiled[0].data_ptr(), self._tiled[1].data_ptr()
         for name in ("U64", "V64", "Up64", "Vp64", "U", "V", "Upanel", "Vpanel", "scaleU", "scaleV", "wsU", "wsV", "Mslab", "Nslab", "gram_slabs",
                      "GU", "GV", "GU64", "GV64", "normsU", "normsV", "partU", "partV", "dotpart", "ubits", "vbits", "ucolbits", "vcolbits", "counts"):
             setattr(st, name, getattr(self, name).data_ptr())
-        st.log = self._log_host.data_ptr()
+        st.log = self._ring.host.data_ptr()
         st.beta, st.thr_u, st.thr_v = self.beta, float(self.thr[0]), float(self.thr[1])
         self._st = st
-        self._events = [None] * self.LOG_ROWS
         self._last = -1
         self._lag = lib.bmf_palm_row_lag(C.byref(st)) if self.variant == L.PALM_ELBMF else 0
         if self._lag < 0:
@@ -115,16 +112,14 @@ class PalmEngine:
         st = self._state()
         with torch.cuda.device(self.device):
             check(lib.bmf_primp_iterate(C.byref(st), int(it), float(l1), float(l2), _stream()), "bmf_primp_iterate")
-            self._mark(it)
+            self._ring.mark(it)
         self._last = it
 
     def primp_row(self, it: int) -> float:
         """||X - U V^T||_F^2 after iteration `it`."""
-        slot = it % self.LOG_ROWS
-        if self._events[slot] is None or self._events[slot][0] != it:
+        if not self._ring.has(it):
             raise RuntimeError(f"row {it} is not available (last iteration enqueued: {self._last})")
-        self._events[slot][1].synchronize()
-        return self._decode(self._log_host[slot].numpy().copy(), False)[0]
+        return self._decode(self._ring.wait(it), False)[0]
 
     def keep(self):
         """Snapshot the current factors (device copies, in stream order): what a loop that has already enqueued the next iteration
@@ -150,28 +145,21 @@ class PalmEngine:
             s = _stream()
             check(lib.bmf_palm_iterate(*args, 1, s), "bmf_palm_iterate")
             if self._lag and it > 0:
-                self._mark(it - 1)
+                self._ring.mark(it - 1)
             check(lib.bmf_palm_iterate(*args, 2, s), "bmf_palm_iterate")
             if not self._lag:
-                self._mark(it)
+                self._ring.mark(it)
         self._last = it
-
-    def _mark(self, it):
-        ev = torch.cuda.Event()
-        ev.record()
-        self._events[it % self.LOG_ROWS] = (it, ev)
 
     def row(self, it: int):
         """(err, U gap, V gap, (TP, FP, FN, TN)) of iteration `it`, as ``scalars`` returns them."""
-        slot = it % self.LOG_ROWS
-        if self._events[slot] is None or self._events[slot][0] != it:
+        if not self._ring.has(it):
             if not (self._lag and it == self._last):
                 raise RuntimeError(f"row {it} is not available (last iteration enqueued: {self._last})")
             with torch.cuda.device(self.device):   # the last iteration: no later U step will complete its row
                 check(lib.bmf_palm_finish_row(C.byref(self._st), int(it), _stream()), "bmf_palm_finish_row")
-                self._mark(it)
-        self._events[slot][1].synchronize()
-        return self._decode(self._log_host[slot].numpy().copy(), True)
+                self._ring.mark(it)
+        return self._decode(self._ring.wait(it), True)
 
     def previous_factors(self):
         """The iterate before the current one (Up64 / Vp64): what a loop that ran one iteration past its stopping rule returns."""

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib as L
 from ._lib import lib, check, ptr
-from .engine import BitMatrix, _stream, xf_slots_i8
+from .engine import BitMatrix, HostRows, _stream, xf_slots_i8
 
 MAX_K_WIDE = 128
 BK = 64   # columns of a block
@@ -157,19 +157,16 @@ class WideMUEngine:
                 self._refresh(which)
 
     # ---- the loop without a host round trip per iteration (round 5): iteration t + 1 is enqueued before the scalars of t are read ----
-    LOG_ROWS = 8
-
     def can_pipeline(self):
         return True
 
     def iterate(self, it: int, reg: float, update: bool = True):
         """Enqueue iteration `it`: keep the current iterate, update (unless update = False: log row 0), gather the scalars into a pinned
         host row with an asynchronous copy + event.  ``row(it, reg)`` waits for that row only (the protocol of MaskedMUEngine /
-        LinkMUEngine, driven by BinaryMFPenalty._fit_masked / WNMF._fit_masked)."""
+        LinkMUEngine, driven by ContinuousModel.mu_loop)."""
         with torch.cuda.device(self.device):
-            if getattr(self, "_rows_host", None) is None:
-                self._rows_host = torch.zeros((self.LOG_ROWS, 8), dtype=torch.float64).pin_memory()
-                self._events = [None] * self.LOG_ROWS
+            if getattr(self, "_ring", None) is None:
+                self._ring = HostRows()
                 self._Up = [torch.empty_like(t) for t in self.U64]
                 self._Vp = [torch.empty_like(t) for t in self.V64]
             if update:
@@ -178,18 +175,11 @@ class WideMUEngine:
                     self._Vp[b].copy_(self.V64[b], non_blocking=True)
                 self.update(reg)
             self._gather_scalars()
-            slot = it % self.LOG_ROWS
-            self._rows_host[slot].copy_(self._scal, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._events[slot] = (it, ev)
+            self._ring.slot(it).copy_(self._scal, non_blocking=True)
+            self._ring.mark(it)
 
     def row(self, it: int, reg: float):
-        slot = it % self.LOG_ROWS
-        if self._events[slot] is None or self._events[slot][0] != it:
-            raise RuntimeError(f"row {it} is not available")
-        self._events[slot][1].synchronize()
-        return self._decode(self._rows_host[slot].numpy().copy(), reg)
+        return self._decode(self._ring.wait(it), reg)
 
     def previous_factors(self):
         """The iterate before the last enqueued update."""
@@ -299,6 +289,9 @@ class WideMaskedMUEngine:
         U = torch.cat([self.U64[b][: self.m, : self.kb[b]] for b in range(2)], dim=1).cpu().numpy()
         V = torch.cat([self.V64[b][: self.n, : self.kb[b]] for b in range(2)], dim=1).cpu().numpy()
         return U, V
+
+    def can_pipeline(self):
+        return False
 
     def _pass(self, ls, rows, Fself, Fother, num, den, sums):
         if sums is not None:

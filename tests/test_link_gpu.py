@@ -320,6 +320,7 @@ def test_link_loops_in_c_calls_take_the_same_path_as_the_stepwise_loops(monkeypa
     """PNLPF and WNMF-KL enqueue whole iterations by one C call each (bmf_link_iterate) and read the scalars of iteration t while t + 1
     runs; the loop overshoots its stopping rule by one iteration and returns the iterate before.  Same kernels in the same order as the
     stepwise loop: stopping iteration and factors bit for bit, log rows to 1e-12 (their sums are fp64 atomic accumulations)."""
+    from pybmf_amd.engine import LinkMUEngine
     from pybmf_amd.models import PNLPF, WNMF
     rs = np.random.RandomState(21)
     m, n, k = 420, 310, 10
@@ -328,7 +329,8 @@ def test_link_loops_in_c_calls_take_the_same_path_as_the_stepwise_loops(monkeypa
     V0 = np.abs(rs.standard_normal((n, k))) * 0.3 + 1e-3
     out = {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("BMF_LINK_PIPELINE", flag)
+        if flag == "0":   # the stepwise loops
+            monkeypatch.setattr(LinkMUEngine, "can_pipeline", lambda self: False)
         with quiet():
             p = PNLPF(k=k, U=U0.copy(), V=V0.copy(), W="full", reg=1.0, reg_growth=1.3, link_lamda=10, init_method="custom", normalize_method=None,
                       max_iter=12, tol=0.0)

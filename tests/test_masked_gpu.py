@@ -263,6 +263,7 @@ def test_masked_loop_in_c_calls_takes_the_same_path_as_the_stepwise_loop(monkeyp
     """BinaryMFPenalty and WNMF under W='mask' enqueue whole iterations by one C call each (bmf_masked_iterate) and read the scalars of
     iteration t while t + 1 runs, so the loop overshoots its stopping rule by one iteration and returns the iterate before.  Same
     kernels in the same order as the stepwise loop: stopping iteration and factors must be identical, bit for bit; the log rows to 1e-12."""
+    from pybmf_amd.engine import MaskedMUEngine
     from pybmf_amd.models import BinaryMFPenalty, WNMF
     rs = np.random.RandomState(5)
     m, n, k = 700, 500, 12
@@ -274,7 +275,8 @@ def test_masked_loop_in_c_calls_takes_the_same_path_as_the_stepwise_loop(monkeyp
     V0 = np.abs(rs.standard_normal((n, k))) * 0.3 + 1e-3
     out = {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("BMF_MASKED_PIPELINE", flag)
+        if flag == "0":   # the stepwise loop
+            monkeypatch.setattr(MaskedMUEngine, "can_pipeline", lambda self: False)
         with quiet():
             p = BinaryMFPenalty(k=k, U=U0.copy(), V=V0.copy(), W="mask", reg=1.0, reg_growth=1.5, init_method="custom", normalize_method=None,
                                 max_iter=40, tol=0.0, min_diff=1e-3)
@@ -295,6 +297,7 @@ def test_masked_loop_in_c_calls_on_a_real_valued_matrix(monkeypatch):
     """The same equality for WNMF under W='mask' on REAL-valued data (the whole-matrix scores then run on the fp32 copy of X,
     bmf_masked_loop.Xreal), with an early stop before max_iter so that the overshoot-and-return-the-previous-iterate path is the one
     that ends the fit."""
+    from pybmf_amd.engine import MaskedMUEngine
     from pybmf_amd.models import WNMF
     rs = np.random.RandomState(11)
     m, n, k = 400, 260, 8
@@ -306,7 +309,8 @@ def test_masked_loop_in_c_calls_on_a_real_valued_matrix(monkeypatch):
     V0 = np.abs(rs.standard_normal((n, k))) * 0.5 + 1e-2
     out = {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("BMF_MASKED_PIPELINE", flag)
+        if flag == "0":   # the stepwise loop
+            monkeypatch.setattr(MaskedMUEngine, "can_pipeline", lambda self: False)
         with quiet():
             w = WNMF(k=k, U=U0.copy(), V=V0.copy(), W="mask", init_method="custom", max_iter=200, min_diff=5.0)
             w.fit(X.copy(), **FIT)

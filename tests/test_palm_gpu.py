@@ -309,13 +309,15 @@ def test_elbmf_one_call_iteration_matches_the_stepwise_engine(m, n, k, beta):
 def test_elbmf_class_loops_agree(monkeypatch):
     """ELBMF.fit through the one-call loop (default) and through the stepwise Python loop: same number of iterations, same log, same factors."""
     from pybmf_amd.models import ELBMF
+    from pybmf_amd.palm import PalmEngine
     rs = np.random.RandomState(23)
     m, n, k = 600, 380, 12
     X = ((rs.rand(m, 6) < 0.25).astype(int) @ (rs.rand(6, n) < 0.25).astype(int) > 0).astype(np.uint8)
     U0, V0 = rs.rand(m, k) * 0.5, rs.rand(n, k) * 0.5
     out = {}
     for loop in ("c", "python"):
-        monkeypatch.setenv("BMF_PALM_LOOP", loop)
+        if loop == "python":   # the stepwise loop
+            monkeypatch.setattr(PalmEngine, "can_pipeline", lambda self: False)
         with quiet():
             mdl = ELBMF(k=k, U=U0.copy(), V=V0.copy(), W="full", init_method="custom", reg_l1=0.01, reg_l2=0.02, reg_growth=1.3, beta=0.0,
                         max_iter=200, min_diff=1e-3, tol=0.0)
