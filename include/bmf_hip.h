@@ -671,6 +671,29 @@ int bmf_masked_thresh64_k(const int64_t* ptr, const int32_t* idx, const float* v
                           const int64_t* seg_beg, int32_t nseg, const double* Us, const double* dUs, const double* Vs, const double* dVs,
                           int kp, int kcols, double* partial, int32_t partial_blocks, double* out, void* stream);
 
+/* ---- FastStep: the logistic loss of one factor, for the projected line search (csrc/faststep.hip) ---------------------------
+ * PyBMF/models/FastStep.py:147-211.  With M = 2 X - 1, S = U V^T where column k of the factors is replaced by the candidate (u, v),
+ * and a = -M o (S - tau):
+ *   F  = sum over ALL m x n cells of log(1 + exp(W o a))          (a cell the mask leaves out adds log 2)
+ *   G  = W o (-M o sigmoid(a)),   du = G v,   dv = G^T u
+ *   TP / FP = cells with S > tau where X is 1 / 0                   (the whole matrix, whatever the mask)
+ * Only column k moves during a factor's search, so S - tau = B + u v^T with B fixed; fp64 end to end (the search compares F values
+ * that differ by min_diff = 1e-2 on F of 1e3 .. 1e7), every sum in a fixed order, no atomics: a call repeated on the same input
+ * returns the same bits. */
+
+/* B (m_pad x n_pad fp64, row stride n_pad) = U64 V64^T - tau without latent column `skip` (-1: none left out), over the tiles that
+ * hold the m x n real cells.  U64 / V64: m_pad x kp, n_pad x kp fp64, zero padded; m_pad, n_pad multiples of 128; kp 32 or 64. */
+int bmf_faststep_base(const double* U64, const double* V64, int64_t m_pad, int64_t n_pad, int32_t m, int32_t n, int k, int kp, int skip,
+                      double tau, double* B, void* stream);
+/* One sweep over B and the bits of X (row stride ldx words, ldx * 32 >= n_pad) and, Wbits != NULL, the bits of the mask (same
+ * layout).  u: m doubles, v: n doubles (device).  F: 1 double.  want_grad: du (m doubles), dv (n doubles).  want_counts: counts[0] =
+ * TP, counts[1] = FP.  work: bmf_faststep_eval_work() doubles of scratch -- the per-stripe partial slabs of the row sums and the
+ * column sums and the per-tile partials of F and the counts, which a second kernel adds in a fixed order. */
+int64_t bmf_faststep_eval_work(int64_t m_pad, int64_t n_pad, int32_t m, int32_t n);
+int bmf_faststep_eval(const double* B, const uint32_t* Xbits, const uint32_t* Wbits, int64_t m_pad, int64_t n_pad, int64_t ldx, int32_t m,
+                      int32_t n, const double* u, const double* v, int want_grad, int want_counts, double* work, double* F, double* du,
+                      double* dv, int64_t* counts, void* stream);
+
 /* ---- updates through an element-wise link (PNLPF, WNMF with the Kullback-Leibler loss) ---------------------------------- */
 
 #define BMF_LINK_SIGMOID 1 /* PNLPF: prediction sigmoid(lamda (U V^T - 1/2)), models/PNLPF.py:54-58 */

@@ -6,5 +6,6 @@ from .PNLPF import PNLPF
 from .BinaryMFThreshold import BinaryMFThreshold
 from .ELBMF import ELBMF
 from .PRIMP import PRIMP
+from .FastStep import FastStep
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep"]
