@@ -694,6 +694,31 @@ int bmf_faststep_eval(const double* B, const uint32_t* Xbits, const uint32_t* Wb
                       int32_t n, const double* u, const double* v, int want_grad, int want_counts, double* work, double* F, double* du,
                       double* dv, int64_t* counts, void* stream);
 
+/* ---- GreConD: concept search on bit sets (csrc/grecond.hip) ------------------------------------------------------------------
+ * PyBMF/models/GreConD.py:72-130.  All matrices are TRANSPOSED bit matrices: n (or more) rows of ldw = m_pad / 32 words, row c =
+ * column c of X (BitMatrix.bits_t), zero padded.  A set of rows of X is one such bit row.
+ *
+ * bmf_concept_scan: for every candidate column j = cand[i], i < ncand:  u_j = Xt[j] & best_u,  nu[i] = |u_j|,
+ *   v_j = { c < n : u_j subset of Xt[c] },  nv[i] = |v_j|,  score[i] = sum over c in v_j of |u_j & Xrs_t[c]|;
+ *   rec[0..4] = { i, cand[i], score[i], nu[i], nv[i] } of the FIRST i with score[i] > best_score, or { -1, -1, 0, 0, 0 }.
+ *   work: bmf_concept_scan_work(ncand) bytes, 8-byte aligned.  ldw <= 1008 (32256 padded rows: the LDS of a workgroup is kept within 64 KiB by choice).  Exact integers, no atomics:
+ *   the same input gives the same output.
+ * bmf_concept_close: best_u &= Xt[j] in place; best_v (ceil(n / 64) * 2 words are written) := bit c = (best_u subset of Xt[c]).
+ *   j < 0: the column is rec[1] read on the device (rec of bmf_concept_scan), and nothing is written when that is -1.
+ * bmf_concept_apply: for every c with bit c of v set: Xrs_t[c] &= ~u, Xpd_t[c] |= u;  colcount[c] = |Xrs_t[c]| for all c < n,
+ *   *rsum = their sum.  u == v == NULL: only the counts.
+ * bmf_bits_confusion: counts[0] = |P & G|, counts[1] = |P| over `rows` rows of ldw words; work: 2 * rows int32. */
+int64_t bmf_concept_scan_work(int32_t ncand);
+int bmf_concept_scan(const uint32_t* Xt, const uint32_t* Xrs_t, int32_t n, int64_t ldw, const uint32_t* best_u, const int32_t* cand,
+                     int32_t ncand, int64_t best_score, void* work, int64_t* score, int32_t* nu, int32_t* nv, int64_t* rec,
+                     void* stream);
+int bmf_concept_close(const uint32_t* Xt, int32_t n, int64_t ldw, int32_t j, const int64_t* rec, uint32_t* best_u, uint32_t* best_v,
+                      void* stream);
+int bmf_concept_apply(uint32_t* Xrs_t, uint32_t* Xpd_t, int32_t n, int64_t ldw, const uint32_t* u, const uint32_t* v,
+                      int32_t* colcount, int64_t* rsum, void* stream);
+int bmf_bits_confusion(const uint32_t* Pbits, const uint32_t* Gbits, int32_t rows, int64_t ldw, int32_t* work, int64_t* counts,
+                       void* stream);
+
 /* ---- updates through an element-wise link (PNLPF, WNMF with the Kullback-Leibler loss) ---------------------------------- */
 
 #define BMF_LINK_SIGMOID 1 /* PNLPF: prediction sigmoid(lamda (U V^T - 1/2)), models/PNLPF.py:54-58 */

@@ -238,6 +238,11 @@ SIGNATURES = {
     "bmf_faststep_base": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, C.c_int, C.c_int, C.c_int, _f64, _vp, _vp]),
     "bmf_faststep_eval_work": (_i64, [_i64, _i64, _i32, _i32]),
     "bmf_faststep_eval": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_concept_scan_work": (_i64, [_i32]),
+    "bmf_concept_scan": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_concept_close": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "bmf_concept_apply": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_bits_confusion": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
     "bmf_link_splits": (C.c_int, [_i64, _i64]),
     "bmf_masked_iterate": (C.c_int, [_vp, _f64, C.c_int, _vp, _vp]),
     "bmf_link_iterate": (C.c_int, [_vp, _f64, C.c_int, _vp, _vp]),

@@ -162,3 +162,20 @@ class BaseModelTools:
 
     def truncate_factors(self, k):
         self.U, self.V = self.U[:, :k], self.V[:, :k]
+
+    def set_factors(self, k, u, v):
+        """Factor k := (u, v); the factor matrices grow when they have fewer than k + 1 columns (BaseModelTools.py:366-381)."""
+        if self.U.shape[1] < k + 1:
+            self.extend_factors(k + 1)
+        self.U[:, k] = u
+        self.V[:, k] = v
+
+    def extend_factors(self, k):
+        """Empty columns up to k factors (BaseModelTools.py:396-405); scipy lil factors stay lil, arrays stay arrays."""
+        from scipy.sparse import hstack, issparse, lil_matrix
+        if issparse(self.U):
+            self.U = hstack([self.U, lil_matrix((self.m, k - self.U.shape[1]))]).tolil()
+            self.V = hstack([self.V, lil_matrix((self.n, k - self.V.shape[1]))]).tolil()
+        else:
+            self.U = np.hstack([self.U, np.zeros((self.m, k - self.U.shape[1]), dtype=self.U.dtype)])
+            self.V = np.hstack([self.V, np.zeros((self.n, k - self.V.shape[1]), dtype=self.V.dtype)])

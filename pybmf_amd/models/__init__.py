@@ -7,5 +7,6 @@ from .BinaryMFThreshold import BinaryMFThreshold
 from .ELBMF import ELBMF
 from .PRIMP import PRIMP
 from .FastStep import FastStep
+from .GreConD import GreConD
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD"]
