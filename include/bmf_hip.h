@@ -719,6 +719,35 @@ int bmf_concept_apply(uint32_t* Xrs_t, uint32_t* Xpd_t, int32_t n, int64_t ldw, 
 int bmf_bits_confusion(const uint32_t* Pbits, const uint32_t* Gbits, int32_t rows, int64_t ldw, int32_t* work, int64_t* counts,
                        void* stream);
 
+/* ---- Asso: candidate basis rows and their scores (csrc/asso.hip) ------------------------------------------------------------------
+ * PyBMF/models/Asso.py:62-235 with basis_dim = 1.  X, the prediction PD and the candidate matrix B are ROW-MAJOR bit matrices of ldx =
+ * n_pad / 32 words per row (a multiple of 16, 16-byte aligned); only bmf_asso_basis reads the transposed bits of X (BitMatrix.bits_t:
+ * one row of ldw = m_pad / 32 words per column).  Exact integers, fp64 only where the reference compares in fp64, no atomics: the same
+ * input gives the same bytes.
+ *
+ * bmf_asso_basis: bit j of row i of B := C[i][j] / C[i][i] > tau (fp64 division, strict; an empty column gives an empty row), C = X^T X
+ *   counted tile by tile and never stored; bits j >= n stay 0.  count[i] = |B_i| for i < n.  B: n rows of ldb words.
+ * bmf_asso_score: for every candidate b = B[cand[i]], i < ncand, and every row r < m:  a = |x_r & ~pd_r & b|, c = |~pd_r & b| - a,
+ *   TP_new = tp_old[r] + a, FP_new = fp_old[r] + c; the row takes the candidate iff (-w_fp) FP_new + w_fn TP_new > (-w_fp) FP_old +
+ *   w_fn TP_old, evaluated in fp64 as written (two products, one sum, no FMA).  work receives one int64 pair (sum of the chosen TP, of
+ *   the chosen FP) per (tile of 64 rows, candidate): bmf_asso_score_work(m, ncand) bytes, 8-byte aligned.  tp_old / fp_old: what
+ *   bmf_confusion_rows gives for (X, PD).  A cand[i] outside [0, n_rows_b) scores as an empty candidate.
+ * bmf_asso_pick: T[i], F[i] = the pairs of `work` added in tile order, score[i] = w_fn T[i] - w_fp F[i];  rec[0..4] = { i, cand[i],
+ *   the bits of score[i], T[i], F[i] } of the largest score above best_score, the first of equals (what the reference's sweep keeps),
+ *   or { -1, -1, the bits of best_score, 0, 0 }.
+ * bmf_asso_column: the per-row decision of bmf_asso_score for the one candidate b (ldx words), as bits: ceil(m / 32) words of u are
+ *   written, *nu = |u|;  work: ceil(m / 32) int32.
+ * bmf_asso_apply: PD_r |= v for every row r < m whose bit of u is set. */
+int bmf_asso_basis(const uint32_t* Xt, int32_t n, int64_t ldw, double tau, uint32_t* B, int64_t ldb, int32_t* count, void* stream);
+int64_t bmf_asso_score_work(int32_t m, int32_t ncand);
+int bmf_asso_score(const uint32_t* X, const uint32_t* PD, const uint32_t* B, int64_t ldx, int32_t m, int32_t n_rows_b, const int32_t* cand,
+                   int32_t ncand, const uint32_t* tp_old, const uint32_t* fp_old, double w_fp, double w_fn, void* work, void* stream);
+int bmf_asso_pick(const void* work, int32_t m, const int32_t* cand, int32_t ncand, double best_score, double w_fp, double w_fn, int64_t* T,
+                  int64_t* F, double* score, int64_t* rec, void* stream);
+int bmf_asso_column(const uint32_t* X, const uint32_t* PD, const uint32_t* b, int64_t ldx, int32_t m, const uint32_t* tp_old,
+                    const uint32_t* fp_old, double w_fp, double w_fn, uint32_t* u, int32_t* work, int64_t* nu, void* stream);
+int bmf_asso_apply(uint32_t* PD, int64_t ldx, int32_t m, const uint32_t* u, const uint32_t* v, void* stream);
+
 /* ---- updates through an element-wise link (PNLPF, WNMF with the Kullback-Leibler loss) ---------------------------------- */
 
 #define BMF_LINK_SIGMOID 1 /* PNLPF: prediction sigmoid(lamda (U V^T - 1/2)), models/PNLPF.py:54-58 */

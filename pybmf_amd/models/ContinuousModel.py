@@ -365,6 +365,11 @@ class ContinuousModel(BaseModel):
             r, p, a, f1 = scores_from_counts(*counts)
             out.update({"TP": tp, "FP": fp, "FN": fn, "TN": tn, "Recall": r, "Precision": p, "Accuracy": a, "F1": f1,
                         "TPR": r, "PPV": p, "ACC": a})
+            if len(counts) == 4:
+                # integer counts; utils/metrics.py:86-125 of the reference: FPR = 1 - TNR (TNR is 0 without a negative cell), FNR = 1 - TPR,
+                # ERR = 1 - ACC
+                n_neg = int(fp) + int(tn)
+                out.update({"FPR": 1 - (np.float64(tn) / n_neg if n_neg > 0 else 0), "FNR": 1 - r, "ERR": 1 - a})
         return [out.get(mt) for mt in metrics]
 
     def _engine_scores(self, eng, want_real=True, want_boolean=True, link=None, lamda=0.0):

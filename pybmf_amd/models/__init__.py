@@ -8,5 +8,6 @@ from .ELBMF import ELBMF
 from .PRIMP import PRIMP
 from .FastStep import FastStep
 from .GreConD import GreConD
+from .Asso import Asso
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso"]
