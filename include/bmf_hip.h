@@ -748,6 +748,30 @@ int bmf_asso_column(const uint32_t* X, const uint32_t* PD, const uint32_t* b, in
                     const uint32_t* fp_old, double w_fp, double w_fn, uint32_t* u, int32_t* work, int64_t* nu, void* stream);
 int bmf_asso_apply(uint32_t* PD, int64_t ldx, int32_t m, const uint32_t* u, const uint32_t* v, void* stream);
 
+/* ---- AssoIter / AssoOpt: U of an Asso model re-decided against fixed V (csrc/asso_refine.hip) ---------------------------------------
+ * PyBMF/models/AssoIter.py:80-100 and AssoOpt.py:69-80.  X: row-major bits, ldx = n_pad / 32 words per row (a multiple of 16, 16-byte
+ * aligned).  V: one bit row of ldx words per FACTOR, k rows.  U: one mask of kw = ceil(k / 32) words per row of X, bit l = U[r][l]; bits
+ * >= k are ignored.  The V rows are staged in LDS `chunk` words at a time, at most 60 KiB per workgroup; chunk = 0 takes the largest
+ * that fits (all ldx words when k n_pad bits fit), any smaller multiple of 4 gives the same result.  Exact integers, the row score
+ * (-w_fp) FP + w_fn TP in fp64 as written (two products, one sum, no FMA), fixed summation order, no atomics.
+ *
+ * bmf_asso_refine_chunk: the chunk that chunk = 0 stands for (rows_kernel: of bmf_asso_refine_rows, else of bmf_asso_refine_column), or
+ *   -1 when k is beyond the kernel's limit (1024 for the column kernel, 16 for the row search) or ldx is not a multiple of 16.
+ * bmf_asso_refine_column: for every row r < m, X_old = OR of the V rows its mask selects without factor kc, X_new = X_old | V[kc]; the
+ *   row takes factor kc iff score(X_new) > score(X_old), strict.  Bit kc of every mask is REPLACED by that decision; u receives the
+ *   decisions as ceil(m / 32) packed words.  rec[0..3] = { the bits of w_fn T - w_fp F, T, F, |u| }, T / F = TP / FP of the prediction
+ *   after the replacement.  part: 3 * ceil(m / 32) int64.
+ * bmf_asso_refine_rows: k <= 16, kw = 1.  For every row r < m, j[r] = the first j in [0, 2^k) with the largest score of the OR of the
+ *   V rows in j against x_r, factor l being bit k - 1 - l of j (factor 0 the most significant); U[r] := that subset as a mask.
+ *   rec[0..3] = { the bits of w_fn T - w_fp F, T, F, the ones of U } of the new prediction.  part: 3 * m int64.
+ * bmf_asso_refine_product: PD_r = OR of the V rows that the mask of row r selects, r < m (ldx words per row). */
+int bmf_asso_refine_chunk(int32_t k, int64_t ldx, int32_t rows_kernel);
+int bmf_asso_refine_column(const uint32_t* X, int64_t ldx, int32_t m, const uint32_t* V, int32_t k, uint32_t* U, int32_t kw, int32_t kc,
+                           int32_t chunk, double w_fp, double w_fn, uint32_t* u, int64_t* part, int64_t* rec, void* stream);
+int bmf_asso_refine_rows(const uint32_t* X, int64_t ldx, int32_t m, const uint32_t* V, int32_t k, int32_t chunk, double w_fp, double w_fn,
+                         int32_t* j, uint32_t* U, int64_t* part, int64_t* rec, void* stream);
+int bmf_asso_refine_product(const uint32_t* U, int32_t kw, const uint32_t* V, int32_t k, int64_t ldx, int32_t m, uint32_t* PD, void* stream);
+
 /* ---- updates through an element-wise link (PNLPF, WNMF with the Kullback-Leibler loss) ---------------------------------- */
 
 #define BMF_LINK_SIGMOID 1 /* PNLPF: prediction sigmoid(lamda (U V^T - 1/2)), models/PNLPF.py:54-58 */

@@ -249,6 +249,10 @@ SIGNATURES = {
     "bmf_asso_pick": (C.c_int, [_vp, _i32, _vp, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp]),
     "bmf_asso_column": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
     "bmf_asso_apply": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "bmf_asso_refine_chunk": (C.c_int, [_i32, _i64, _i32]),
+    "bmf_asso_refine_column": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "bmf_asso_refine_rows": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_asso_refine_product": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp]),
     "bmf_link_splits": (C.c_int, [_i64, _i64]),
     "bmf_masked_iterate": (C.c_int, [_vp, _f64, C.c_int, _vp, _vp]),
     "bmf_link_iterate": (C.c_int, [_vp, _f64, C.c_int, _vp, _vp]),

@@ -9,5 +9,7 @@ from .PRIMP import PRIMP
 from .FastStep import FastStep
 from .GreConD import GreConD
 from .Asso import Asso
+from .AssoIter import AssoIter
+from .AssoOpt import AssoOpt
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso", "AssoIter", "AssoOpt"]
