@@ -10,6 +10,7 @@ import time
 import numpy as np
 import pytest
 
+from boolean_family import grecond_invariants
 from test_grecond_cpu import (NumpyConceptEngine, check_fit, close_concept, fit_case, load_case, log_rows, pack_rows, popcount, scan_block,
                               unpack)
 
@@ -208,24 +209,9 @@ def test_ml1m_shape_invariants():
     assert len(rows) == k
     U, V = np.asarray(model.U.todense()) != 0, np.asarray(model.V.todense()) != 0
     assert U.shape == (X.shape[0], k) and V.shape == (X.shape[1], k)
-    Xb = X != 0
-    covered = np.zeros_like(Xb)
-    sum_x, resid = int(Xb.sum()), int(Xb.sum())
-    for f, r in enumerate(rows):
-        u, v = U[:, f], V[:, f]
-        assert r[0] == f and r[1] >= 1 and [r[2], r[3]] == [int(u.sum()), int(v.sum())]
-        assert Xb[np.ix_(u, v)].all()                                            # a rectangle of ones of X
-        assert not (Xb[:, v].all(axis=1) & ~u).any() and not (Xb[u].all(axis=0) & ~v).any()   # closed: no row / column can be added
-        covered[np.ix_(u, v)] = True
-        now = sum_x - int(covered.sum())
-        assert r[1] == resid - now                                               # score = the drop of the residual sum
-        resid = now
-        recall, precision = r[4], r[5]
-        assert precision == 1.0 and abs(recall - (sum_x - resid) / sum_x) <= 1e-12   # FP = 0 on train in every row
-    tp, fp, fn, tn = model._engine.counts("train")
-    assert (tp, fp, fn, tn) == (int(covered.sum()), 0, resid, X.size - sum_x) and model._engine.residual_sum() == resid
-    X_pd = np.asarray(model.X_pd.todense()) != 0
-    assert (X_pd == covered).all()
+    # every factor a closed rectangle of ones, score = the drop of the residual sum, FP = 0 in every row, the counts and the prediction
+    covered = grecond_invariants(X, rows, U, V, model._engine.counts("train"), model._engine.residual_sum(), np.asarray(model.X_pd.todense()))
+    assert int(covered.sum()) == model._engine.counts("train")[0]
     # the first three concepts against the stand-in, and block sizes against each other
     from pybmf_amd.engine import BitMatrix
     from pybmf_amd.grecond import ConceptEngine
