@@ -719,6 +719,30 @@ int bmf_concept_apply(uint32_t* Xrs_t, uint32_t* Xpd_t, int32_t n, int64_t ldw, 
 int bmf_bits_confusion(const uint32_t* Pbits, const uint32_t* Gbits, int32_t rows, int64_t ldw, int32_t* work, int64_t* counts,
                        void* stream);
 
+/* ---- MEBF: median expansion on residual bit sets (csrc/mebf.hip) ---------------------------------------------------------------
+ * PyBMF/models/MEBF.py:112-231.  A growth along one axis reads the bit matrices of ONE orientation: N bit rows of ld words, zero
+ * padded (axis 0: the transposed matrices, bit row j = column j of X, ld = m_pad / 32; axis 1: the row-major ones).  rs = residual,
+ * x = data, pd = cover.  Exact integers; the one fp64 decision is (double)count > t * (double)|a|; no atomics.
+ *
+ * bmf_mebf_scores: score[j] = |R_j| for j < N;  out[0] = their sum, out[1] = the number of positive scores.
+ * bmf_mebf_select: weak == 0: rec[0] = the index at rank P / 2 of the P positive scores under (score descending, index descending),
+ *   -1 when P = 0; rec[1] = P.  weak != 0 (N >= 2): rec[0], rec[1] = the indices at ranks 0 and 1 of all scores.  rec[2..7] = 0.
+ * bmf_mebf_weak_a: a (ld words) = rs[rec[0]] & rs[rec[1]].
+ * bmf_mebf_grow: a_from_rec != 0: a (ld words) = rs[rec[0]] first, all zero when rec[0] < 0.  Then c_j = |rs_j & a|, bit j of b =
+ *   (double)c_j > t * (double)|a|; exactly nbw >= ceil(N / 32) words of b are written, bits >= N zero.  rec[2] = |a|, rec[3] = |b|,
+ *   rec[4] = sum over b of |a & x_j & ~pd_j|, rec[5] = sum over b of |a & ~x_j & ~pd_j|; rec[0], rec[1] stay.  ld a multiple of 4;
+ *   rs, x, pd, a 16-byte aligned; work: bmf_mebf_grow_work(N) bytes.
+ * bmf_mebf_apply: for every j < N with bit j of hit set: rs_j &= ~mask, pd_j |= mask, score[j] = |rs_j|, pdcount[j] = |pd_j|; the
+ *   other rows are not touched.  out[0] = sum of score, out[1] = sum of pdcount. */
+int bmf_mebf_scores(const uint32_t* R, int32_t N, int64_t ld, int32_t* score, int64_t* out, void* stream);
+int bmf_mebf_select(const int32_t* score, int32_t N, int32_t weak, int64_t* rec, void* stream);
+int bmf_mebf_weak_a(const uint32_t* rs, int64_t ld, const int64_t* rec, uint32_t* a, void* stream);
+int64_t bmf_mebf_grow_work(int32_t N);
+int bmf_mebf_grow(const uint32_t* rs, const uint32_t* x, const uint32_t* pd, int32_t N, int64_t ld, uint32_t* a, int32_t a_from_rec,
+                  double t, void* work, uint32_t* b, int32_t nbw, int64_t* rec, void* stream);
+int bmf_mebf_apply(uint32_t* rs, uint32_t* pd, int32_t N, int64_t ld, const uint32_t* hit, const uint32_t* mask, int32_t* score,
+                   int32_t* pdcount, int64_t* out, void* stream);
+
 /* ---- Asso: candidate basis rows and their scores (csrc/asso.hip) ------------------------------------------------------------------
  * PyBMF/models/Asso.py:62-235 with basis_dim = 1.  X, the prediction PD and the candidate matrix B are ROW-MAJOR bit matrices of ldx =
  * n_pad / 32 words per row (a multiple of 16, 16-byte aligned); only bmf_asso_basis reads the transposed bits of X (BitMatrix.bits_t:

@@ -11,5 +11,6 @@ from .GreConD import GreConD
 from .Asso import Asso
 from .AssoIter import AssoIter
 from .AssoOpt import AssoOpt
+from .MEBF import MEBF
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso", "AssoIter", "AssoOpt"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso", "AssoIter", "AssoOpt", "MEBF"]
