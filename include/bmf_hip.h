@@ -931,7 +931,8 @@ int bmf_sym_norms(const double* G64, int kp, double* out, void* stream);
 typedef struct {
     double* F64;         /* rows_pad x kp factor being stepped (fp64 master), updated in place */
     double* Fprev64;     /* rows_pad x kp: the point the inertial term extrapolates from (U_{t-1}); see advance_prev */
-    float* F;            /* out: fp32 shadow of the new factor */
+    float* F;            /* out: fp32 shadow of the new factor.  Also IN when beta = 0 and den = NULL: that form takes the operand of the
+                            F G product from the shadow, which must hold (float)F64 on entry (every step leaves it so); 16-byte aligned */
     int64_t rows_pad;    /* multiple of 128 */
     int32_t rows, k, kp;
     int32_t splits;
@@ -956,9 +957,10 @@ typedef struct {
                             bmf_masked_pass run on Fe (bmf_palm_extrapolate); `num` is then (W o X) G from the same pass (one array,
                             splits = 1) and G is not used: gradient = den - num = multiply(W, Fe G^T - X) G  (ELBMF.py:190) */
     int8_t* planes;      /* optional: emit the int8 digit planes of the new factor here ([3][kp][ldp], the layout of bmf_make_panel_i8) with */
-    int64_t ldp;         /*   the PREDICTED column scales plane_scale[kp] (2^e_c), as bmf_epilogue_args.planes does; needs beta = 0, no den, */
+    int64_t ldp;         /*   the PREDICTED column scales plane_scale[kp] (2^e_c), as bmf_epilogue_args.planes does; needs den = NULL, */
     const float* plane_scale; /* blockmax, rows_pad % 512 == 0.  The caller checks the prediction afterwards (bmf_palm_iterate does). */
-    double* dotpart;     /* optional, with planes: [rows_pad/128] per-block sums of F_old o num = <F, X G> of the state BEFORE this step */
+    double* dotpart;     /* optional, needs den = NULL: [rows_pad/128] per-block sums of F_old o num over ALL rows_pad x kp cells of the block
+                            (the padding of F64 is zero on entry: every step leaves it so) = <F, X G> of the state BEFORE this step */
 } bmf_palm_args;
 
 /* One proximal gradient step of one factor:  Fe = F + beta (F - Fprev);  Fn = prox(Fe - eta (Fe G - num), l1 eta, l2 eta),
