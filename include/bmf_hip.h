@@ -743,6 +743,37 @@ int bmf_mebf_grow(const uint32_t* rs, const uint32_t* x, const uint32_t* pd, int
 int bmf_mebf_apply(uint32_t* rs, uint32_t* pd, int32_t N, int64_t ld, const uint32_t* hit, const uint32_t* mask, int32_t* score,
                    int32_t* pdcount, int64_t* out, void* stream);
 
+/* ---- Panda: core and extension scans on bit sets (csrc/panda.hip) ---------------------------------------------------------------
+ * PyBMF/models/Panda.py:162-334.  rs_t, pd_t: the residual and the cover transposed (n or more bit rows of ld = m_pad / 32 words, bit
+ * row c = column c of X); rs, pd: the same row-major (m or more bit rows of ldr = n_pad / 32 words); zero padded.  T: a set of rows
+ * (ld words), I: a set of columns (ldr words).  Exact integers; every decision is the reference's fp64 expression, products and sums
+ * in its order, never an FMA; no atomics.  A scan takes the candidates cand[0 .. count) in list order.
+ *
+ * bmf_panda_couples: out[c] = the sum of rowcount[r] over the set bits r < m of rs_t[c], minus |rs_t[c]|, for c < n.
+ * bmf_panda_core_scan: h1[i] = |T & rs_t[cand[i]]|;  d_cost(h) = w_model ((w0 + 1 + h) - (w0 + h0)) - w_fn ((w0 + 1) h - w0 h0).
+ *   mode 0: the winner is the FIRST i with d_cost(h1[i]) <= 0.  mode 1 (correlation): the pick is the highest h1, among equals the
+ *   LAST position; it is the winner iff its d_cost <= 0.  rec[0..3] = { winner's position or -1, its column or -1, its h1 or 0, the
+ *   pick's position (mode 0: the winner's) }, rec[4..7] = 0.  ld a multiple of 4; rs_t, T 16-byte aligned.
+ * bmf_panda_close: T &= rs_t[j] in place, rec[4] = |T|.  j < 0: the column is rec[1] read on the device, and T stays when that is -1.
+ * bmf_panda_ext_scan: a[i] = |T & rs_t[cand[i]]|, b[i] = |T & pd_t[cand[i]]|;  partial_fn = -a, partial_fp = n_t - b + partial_fn,
+ *   cost_new = cost_old + w_model 1 + w_fp partial_fp + w_fn partial_fn;  rec[0..3] = { position of the FIRST i with cost_new <=
+ *   cost_old or -1, its column or -1, its a, its b }, rec[4..7] = 0.
+ * bmf_panda_rows: column j (j < 0: rec[1] read on the device) joins I, which then holds n_i columns; for every row r < m outside T:
+ *   d_fn = -|rs_r & I|, d_fp = n_i - |pd_r & I| + d_fn, d = w_model 1 + (w_fn d_fn + w_fp d_fp); the rows with d <= 0 are set in T.
+ *   out[0..3] = { their number, sum of d_fn, sum of d_fp, 0 }.  No column (rec[1] = -1): I and T stay, out = 0.  ldr a multiple of
+ *   4; rs, pd, I 16-byte aligned; work: bmf_panda_rows_work(m) bytes. */
+int bmf_panda_couples(const uint32_t* rs_t, int32_t n, int64_t ld, const int32_t* rowcount, int32_t m, int64_t* out, void* stream);
+int bmf_panda_core_scan(const uint32_t* rs_t, int32_t n, int64_t ld, const uint32_t* T, const int32_t* cand, int32_t count, int32_t mode,
+                        double w_model, double w_fn, int64_t w0, int64_t h0, int32_t* h1, int64_t* rec, void* stream);
+int bmf_panda_close(const uint32_t* rs_t, int32_t n, int64_t ld, int32_t j, int64_t* rec, uint32_t* T, void* stream);
+int bmf_panda_ext_scan(const uint32_t* rs_t, const uint32_t* pd_t, int32_t n, int64_t ld, const uint32_t* T, const int32_t* cand,
+                       int32_t count, int64_t n_t, double w_model, double w_fp, double w_fn, double cost_old, int32_t* a, int32_t* b,
+                       int64_t* rec, void* stream);
+int64_t bmf_panda_rows_work(int32_t m);
+int bmf_panda_rows(const uint32_t* rs, const uint32_t* pd, int32_t m, int64_t ldr, int32_t n, int32_t j, const int64_t* rec, uint32_t* I,
+                   int64_t n_i, uint32_t* T, int64_t ldt, double w_model, double w_fp, double w_fn, void* work, int64_t* out,
+                   void* stream);
+
 /* ---- Asso: candidate basis rows and their scores (csrc/asso.hip) ------------------------------------------------------------------
  * PyBMF/models/Asso.py:62-235 with basis_dim = 1.  X, the prediction PD and the candidate matrix B are ROW-MAJOR bit matrices of ldx =
  * n_pad / 32 words per row (a multiple of 16, 16-byte aligned); only bmf_asso_basis reads the transposed bits of X (BitMatrix.bits_t:

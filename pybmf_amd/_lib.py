@@ -249,6 +249,12 @@ SIGNATURES = {
     "bmf_mebf_grow_work": (_i64, [_i32]),
     "bmf_mebf_grow": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _f64, _vp, _vp, _i32, _vp, _vp]),
     "bmf_mebf_apply": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_panda_couples": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _vp, _vp]),
+    "bmf_panda_core_scan": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _i32, _f64, _f64, _i64, _i64, _vp, _vp, _vp]),
+    "bmf_panda_close": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "bmf_panda_ext_scan": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "bmf_panda_rows_work": (_i64, [_i32]),
+    "bmf_panda_rows": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp]),
     "bmf_asso_basis": (C.c_int, [_vp, _i32, _i64, _f64, _vp, _i64, _vp, _vp]),
     "bmf_asso_score_work": (_i64, [_i32, _i32]),
     "bmf_asso_score": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _f64, _f64, _vp, _vp]),

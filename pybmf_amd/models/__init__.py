@@ -12,5 +12,6 @@ from .Asso import Asso
 from .AssoIter import AssoIter
 from .AssoOpt import AssoOpt
 from .MEBF import MEBF
+from .Panda import Panda
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso", "AssoIter", "AssoOpt", "MEBF"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda"]
