@@ -15,9 +15,12 @@
 namespace {
 
 __device__ __forceinline__ void sigmoid_pair(double z, double lam, double& s, double& d) {
-    if (z >= 0) s = 1.0 / (1.0 + exp(-z));
-    else { const double e = exp(z); s = e / (1.0 + e); }
-    d = lam * s * (1.0 - s);   // = lam exp(-z) s^2 (BinaryMFThreshold.py:211-227) without the overflow for z < -709
+    // d = lam exp(-z) s^2 (BinaryMFThreshold.py:211-227) = lam s (1 - s), from e = exp(-|z|) <= 1 on both sides: no overflow for
+    // z < -709, and no 1 - s either -- that difference cancels for z > 0 (relative error 2^-53 / (1 - s): 1e-12 at z = 10, and d = 0
+    // outright beyond z = 37, where the reference still has lam exp(-z))
+    const double e = exp(-fabs(z));
+    if (z >= 0) { s = 1.0 / (1.0 + e); d = lam * e * s * s; }
+    else { s = e / (1.0 + e); d = lam * s / (1.0 + e); }
 }
 
 __global__ __launch_bounds__(256) void transform64_kernel(const double* __restrict__ F, int64_t rows_pad, int rows, int k, int kp,
