@@ -378,10 +378,13 @@ int bmf_cover_launch(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, int64
         const int rows_per_block = (int)(((units + groups - 1) / groups) * 64);
         groups = (rows_pad + rows_per_block - 1) / rows_per_block;
         dim3 grid((unsigned)chunks_w, (unsigned)groups);
+        bool launched = false;
 #define BMF_CW_CASE(N4_, TW_) \
-    if (n4 == N4_ && tw == TW_) launch_cover_wide<N4_, TW_>(grid, s, Xbits, ldx, words, cw, rowbits, colbits, ldcb, kp, rows_pad, rows_per_block, counts, stop);
+    if (n4 == N4_ && tw == TW_) { launch_cover_wide<N4_, TW_>(grid, s, Xbits, ldx, words, cw, rowbits, colbits, ldcb, kp, rows_pad, rows_per_block, counts, stop); launched = true; }
         BMF_CW_CASE(0, 2) BMF_CW_CASE(0, 4) BMF_CW_CASE(1, 0) BMF_CW_CASE(1, 2) BMF_CW_CASE(1, 4) BMF_CW_CASE(2, 0) BMF_CW_CASE(2, 2)
 #undef BMF_CW_CASE
+        // (a chunk size without an instantiation would leave the counts as they were: an error, not a silent zero)
+        BMF_REQUIRE(launched, "bmf_cover_count: no kernel for chunks of %d words (segments %d, tail %d) at words=%lld", cw, n4, tw, (long long)words);
         BMF_LAUNCH_CHECK();
         return BMF_OK;
     }

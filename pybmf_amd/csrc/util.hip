@@ -443,7 +443,7 @@ extern "C" int bmf_gram_partial(const float* F, int64_t rows_pad, int64_t ldf, i
 }
 
 
-// ---- 0.5 * sum(W o (A - B)^2) for dense fp64 arrays: rec_error(X_gt, X_pd, W) with an explicit prediction ---------------------
+// ---- sum(W o (A - B)^2) for dense fp64 arrays: rec_error(X_gt, X_pd, W) with an explicit prediction (the caller applies the 0.5) ---
 namespace {
 constexpr int SQD_BLOCKS = 1024;
 __global__ __launch_bounds__(256) void sqdiff_partial_kernel(const double* __restrict__ A, const double* __restrict__ B,
