@@ -838,7 +838,8 @@ int bmf_asso_refine_product(const uint32_t* U, int32_t kw, const uint32_t* V, in
  *     den = lamda (sig o d) F_other    = link_lamda * multiply(W, multiply(sig, d_sig)) @ V      models/PNLPF.py:68,84
  *   BMF_LINK_KL:      num = (X / (F_self F_other^T)) F_other = (WX / UV) @ V                     models/WNMF.py:117,125
  *     (den is not written: it is the column-sum vector of F_other, bmf_colsum_fill)
- * for the all-ones mask W.  The m x n intermediates are never materialised; exact-fp32 MFMA throughout.  The column range
+ * for the all-ones mask W.  The m x n intermediates are never materialised; exact-fp32 MFMA throughout (for the sigmoid link the MFMA steps of
+ * the product are added in fp64, because lamda multiplies its error: num and den hold rtol 2e-5 up to lamda = 300).  The column range
  * is cut into `splits` = bmf_link_splits(rows, cols) slabs: num / den are [splits][rows_pad][kp] (stride slab_stride), to be
  * summed in slab order.  Xbits: rows_pad x ldx words; F_self: rows_pad x kp, F_other: other_pad x kp (fp32, zero padded). */
 int bmf_link_splits(int64_t rows, int64_t cols);
@@ -849,11 +850,19 @@ int bmf_link_pass(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, int32_t 
 /* The same pass on the 16-bit MFMAs (16x the fp32-MFMA rate) with split operands.  The product P that goes through the link is built
  * from TWO fp16 addends per factor of the factor scaled by a power of two S (max |F| S in [2^14, 2^15): hi = f16(F S), lo = f16(F S - hi);
  * three products hi hi' + hi lo' + lo hi', right to 2^-22 relative to the factors' largest entries; round 4 -- until then three bf16
- * addends and six products), the linear contraction from two bf16 addends (2^-16 per product).
+ * addends and six products), the linear contraction from two bf16 addends per operand (each operand right to 2^-16, a product to
+ * 3 x 2^-16 at worst: the two operands and the lo lo' product that is left out).
  * bmf_link_split makes the copies of one factor the pass needs in ws (5 * rows_pad * kp uint16, 16-byte aligned): [0] fp16 hi and [1] fp16
  * lo, row-major; [2] the first 16 bytes hold {float S, float 1 / S, uint32 bits of max |F|}; [3], [4] the bf16 hi / lo in the
  * reduction order of the contraction.  Call it for a factor whenever that factor changed.  bmf_link_pass16 = bmf_link_pass with the
- * factors given as workspaces. */
+ * factors given as workspaces.
+ * Padding contract of bmf_link_pass16.  Unlike bmf_link_pass, bmf_link_sums and bmf_link_sums16, which mask every cell by rows / cols, the
+ * 16-bit pass has no mask: it relies on zeros.  (a) Every bit of Xbits outside the rows x cols matrix must be 0 in the words it reads --
+ * the bits past `cols` in the last column tile and all bits of rows >= rows -- or num picks up cells that do not exist.  (b) F_other must
+ * be ZERO PADDED when it is split: rows >= cols of the factor given to bmf_link_split / bmf_link_split_pair must be 0 (they are the
+ * columns past `cols` of the last tile; den sums sig d F_other over the whole tile), and so must its columns k .. kp - 1, in both
+ * factors.  The split keeps zeros zero in all four arrays, so zero-padded factors give zero-padded workspaces.  Rows >= rows of num are
+ * then exactly 0; rows >= rows of den are NOT (sig d > 0 there) and must not be read. */
 int bmf_link_split(const float* F, int64_t rows_pad, int kp, uint16_t* ws, void* stream);
 /* The same for BOTH factors of a product at once, with one power-of-two scale per COLUMN pair instead of one per factor: S_k for column k of
  * A, T_k for column k of B, S_k T_k = C for every k (so the kernels divide by one constant), A's columns at full fp16 range, B's at a range

@@ -82,8 +82,23 @@ __global__ __launch_bounds__(256) void link_pass_kernel(const uint32_t* __restri
         f32x16 p;
 #pragma unroll
         for (int i = 0; i < 16; ++i) p[i] = 0.f;
+        // Sigmoid link: s = lam (P - 1/2) multiplies the error of P by lam, and one fp32 ulp of a P near 1/2 times lam = 300 is 2e-5 of d.
+        // So every MFMA step (two products) starts from zero and the steps are added in fp64: the roundings left are those of KH
+        // partial sums of size P / KH, and P - 1/2 is formed before anything is rounded to fp32.  (KL needs no more than fp32.)
+        double pd[16];
+        if (LINK == BMF_LINK_SIGMOID) {
 #pragma unroll
-        for (int s = 0; s < KH; ++s) p = __builtin_amdgcn_mfma_f32_32x32x2f32(b[s], a[s], p, 0, 0, 0);
+            for (int i = 0; i < 16; ++i) pd[i] = 0.0;
+#pragma unroll
+            for (int s = 0; s < KH; ++s) {
+                const f32x16 step = __builtin_amdgcn_mfma_f32_32x32x2f32(b[s], a[s], p, 0, 0, 0);   // p stays zero on this path
+#pragma unroll
+                for (int i = 0; i < 16; ++i) pd[i] += (double)step[i];
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < KH; ++s) p = __builtin_amdgcn_mfma_f32_32x32x2f32(b[s], a[s], p, 0, 0, 0);
+        }
 
         float g1[16], g2[16];
 #pragma unroll
@@ -93,7 +108,7 @@ __global__ __launch_bounds__(256) void link_pass_kernel(const uint32_t* __restri
             const bool x = (xw >> jr) & 1u;
             if (LINK == BMF_LINK_SIGMOID) {
                 float sig, d;
-                sigmoid_parts(lam * (p[i] - 0.5f), sig, d);
+                sigmoid_parts((float)((double)lam * (pd[i] - 0.5)), sig, d);
                 g1[i] = (ok && x) ? lam * d : 0.f;
                 g2[i] = ok ? lam * sig * d : 0.f;
             } else {
