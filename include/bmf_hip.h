@@ -774,6 +774,43 @@ int bmf_panda_rows(const uint32_t* rs, const uint32_t* pd, int32_t m, int64_t ld
                    int64_t n_i, uint32_t* T, int64_t ldt, double w_model, double w_fp, double w_fn, void* work, int64_t* out,
                    void* stream);
 
+/* ---- GreConD+: factor expansion, rebuild and overlap pruning on bit sets (csrc/grecondplus.hip) -----------------------------------
+ * PyBMF/models/GreConDPlus.py:131-308.  A bit matrix is `lines` bit rows of ld words, zero padded: row-major (line = row of X, ld = n_pad
+ * / 32) or transposed (line = column of X, ld = m_pad / 32).  RS = X & ~PD is the residual, which an expansion holds fixed.  Exact
+ * integers; the one fp64 expression is the reference's, products and sums in its order, never an FMA.
+ *
+ * bmf_expand_counts: for every line l < lines and the set s (ld words): abc[l] = |RS_l|, abc[lines + l] = |X_l & (RS_l | s)|,
+ *   abc[2 lines + l] = |s & ~X_l|.  ld a multiple of 4; X, RS, s 16-byte aligned.
+ * bmf_expand_steps: up to `steps` steps of the expansion of (u, v) on one workgroup, no host round trip between them.  A step:
+ *   d_l = ((-w_fp) c_l + w_fn b_l) - ((-w_fp) 0 + w_fn a_l) from the counters of bmf_expand_counts (rows against v, columns against u),
+ *   0.0 for a line inside its own set; r_score / c_score = the highest d of the rows / columns, at its FIRST index.  r_score > c_score
+ *   and r_score > 0: the row joins u and u_exp, and every column j takes its cell: b_j += x & ~rs, c_j += ~x.  c_score > r_score and
+ *   c_score > 0: the column joins v and v_exp, the rows likewise.  Otherwise (equal positive scores included) the expansion stops.
+ *   rec (bmf_expand_rec_words(m, n) int64, zeroed before the first launch): rec[0] = joins, rec[1] = 1 once stopped, rec[2] = steps
+ *   evaluated, rec[3] = 0, then per evaluated step { axis (1 row, 0 column, -1 stop), index or -1, bits of r_score, bits of c_score }.
+ *   A launch after the stop writes nothing.  Every split of the steps over launches gives the same bytes.
+ * bmf_bits_rebuild: for every line l: PD_l = OR of S[k] (ld words each) over the factors k < f whose member set M[k] (ldm words) holds
+ *   l; RS_l = X_l & ~PD_l; count[l] = |RS_l|; *sum = their sum.  PD, count, sum may be null (sum needs count); f = 0: RS = X.
+ * bmf_bits_subset: flag[p] = 1 iff S[set[p]] lies inside X[line[p]], p < count (0 for a pair outside the matrices).
+ * bmf_overlap_counts: cov[i * ldc + j] = the number of factors k < f with bit i of Ub[k] and bit j of Vb[k], i < m, j < n.
+ * bmf_overlap_prune: one factor of remove_overlapped.  u_old := u; every row i of u_exp whose cells (i, j), j in v, are all ones of x
+ *   (row-major bits, ldx words per row) with cov >= 2 leaves u and u_exp, and those counts drop by one; then every column j of v_exp
+ *   whose cells (i, j), i in u_old -- the rows BEFORE the row pass, as in the reference -- are all ones with cov >= 2 leaves v and
+ *   v_exp, and those counts drop by one.  u, u_exp, u_old: ldw words; v, v_exp: ceil(n / 32) words. */
+int bmf_expand_counts(const uint32_t* X, const uint32_t* RS, int32_t lines, int64_t ld, const uint32_t* s, int32_t* abc, void* stream);
+int64_t bmf_expand_rec_words(int32_t m, int32_t n);
+int bmf_expand_steps(const uint32_t* x, const uint32_t* rs, const uint32_t* x_t, const uint32_t* rs_t, int32_t m, int32_t n, int64_t ldx,
+                     int64_t ldw, double w_fp, double w_fn, int32_t steps, int32_t* row_abc, int32_t* col_abc, uint32_t* u, uint32_t* v,
+                     uint32_t* u_exp, uint32_t* v_exp, int64_t* rec, void* stream);
+int bmf_bits_rebuild(const uint32_t* X, int32_t lines, int64_t ld, const uint32_t* S, const uint32_t* M, int64_t ldm, int32_t f,
+                     uint32_t* PD, uint32_t* RS, int32_t* count, int64_t* sum, void* stream);
+int bmf_bits_subset(const uint32_t* X, int32_t lines, int64_t ld, const uint32_t* S, int32_t f, const int32_t* line, const int32_t* set,
+                    int32_t count, int32_t* flag, void* stream);
+int bmf_overlap_counts(const uint32_t* Ub, int64_t ldu, const uint32_t* Vb, int64_t ldv, int32_t f, int32_t m, int32_t n, int32_t* cov,
+                       int64_t ldc, void* stream);
+int bmf_overlap_prune(const uint32_t* x, int64_t ldx, int32_t m, int32_t n, int32_t* cov, int64_t ldc, uint32_t* u, uint32_t* u_exp,
+                      uint32_t* v, uint32_t* v_exp, uint32_t* u_old, int64_t ldw, void* stream);
+
 /* ---- Asso: candidate basis rows and their scores (csrc/asso.hip) ------------------------------------------------------------------
  * PyBMF/models/Asso.py:62-235 with basis_dim = 1.  X, the prediction PD and the candidate matrix B are ROW-MAJOR bit matrices of ldx =
  * n_pad / 32 words per row (a multiple of 16, 16-byte aligned); only bmf_asso_basis reads the transposed bits of X (BitMatrix.bits_t:

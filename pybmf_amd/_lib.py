@@ -255,6 +255,13 @@ SIGNATURES = {
     "bmf_panda_ext_scan": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "bmf_panda_rows_work": (_i64, [_i32]),
     "bmf_panda_rows": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "bmf_expand_counts": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
+    "bmf_expand_rec_words": (_i64, [_i32, _i32]),
+    "bmf_expand_steps": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_bits_rebuild": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_bits_subset": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "bmf_overlap_counts": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "bmf_overlap_prune": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "bmf_asso_basis": (C.c_int, [_vp, _i32, _i64, _f64, _vp, _i64, _vp, _vp]),
     "bmf_asso_score_work": (_i64, [_i32, _i32]),
     "bmf_asso_score": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _f64, _f64, _vp, _vp]),

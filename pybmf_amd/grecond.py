@@ -106,6 +106,25 @@ class ConceptEngine:
         self._refresh_counts(C.c_void_p(base + 4 * self.nvw), C.c_void_p(base))
         self._factors.append((u.copy(), v.copy()))
 
+    def rebuild(self, U_bits, V_bits):
+        """X_pd and X_rs made anew from the factors U_bits (f x W packed words) and V_bits (f x nvw): the only way a prediction shrinks
+        (apply() never restores a residual bit).  The factors replace those applied so far; the per-column counts are refreshed."""
+        U_bits = np.ascontiguousarray(U_bits, dtype=np.uint32).reshape(-1, self.W)
+        V_bits = np.ascontiguousarray(V_bits, dtype=np.uint32).reshape(-1, self.nvw)
+        f = U_bits.shape[0]
+        assert V_bits.shape[0] == f
+        cc = self._colcount
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+            self._fac_u = torch.from_numpy(U_bits.view(np.int32)).to(self.device) if f else None
+            self._fac_v = torch.from_numpy(V_bits.view(np.int32)).to(self.device) if f else None
+            check(lib.bmf_bits_rebuild(ptr(self.bits.bits_t), self.n, self.W, ptr(self._fac_u) if f else None,
+                                       ptr(self._fac_v) if f else None, self.nvw, f, ptr(self.pd_t), ptr(self.rs_t),
+                                       C.c_void_p(cc.data_ptr() + 8), C.c_void_p(cc.data_ptr()), self._stream), "bmf_bits_rebuild")
+            host = cc[: self.n + 2].cpu().numpy()
+        self._rsum = int(host[:2].view(np.int64)[0])
+        self._col_host = host[2:].copy()
+        self._factors = [(U_bits[i].copy(), V_bits[i].copy()) for i in range(f)]
+
     def residual_sum(self) -> int:
         return self._rsum
 

@@ -8,10 +8,11 @@ from .ELBMF import ELBMF
 from .PRIMP import PRIMP
 from .FastStep import FastStep
 from .GreConD import GreConD
+from .GreConDPlus import GreConDPlus
 from .Asso import Asso
 from .AssoIter import AssoIter
 from .AssoOpt import AssoOpt
 from .MEBF import MEBF
 from .Panda import Panda
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda"]
