@@ -271,7 +271,8 @@ typedef struct {
     float* blockmax;   /* optional out: [rows_pad/128][kp] column maxima of the new factor per 128-row block (input of the
                           fp16 / int8 panel builders) */
     int64_t num_block_stride; /* 0: num is [splits][rows_pad][kp]; else num is stored in 32-column blocks, [kp/32][rows_pad][32]
-                          with this many elements between blocks (the sharded exchange buffer); splits must then be 1 */
+                          with this many elements (>= rows_pad * 32) between blocks (the sharded exchange buffer); splits must then
+                          be 1 (both are checked) */
     int8_t* planes;    /* optional out (terms must be 0, blockmax given, rows_pad % 512 == 0): the int8 digit planes of the new factor,
                           [limbs][kp][ldp] in the order of bmf_make_panel_i8, built in-line with the column scales in plane_scale */
     const float* plane_scale; /* [kp]: 2^e_c used for `planes` -- a prediction from the previous iteration's column maxima; the

@@ -528,6 +528,8 @@ extern "C" int bmf_mu_epilogue(const bmf_epilogue_args* a, void* stream) {
     BMF_REQUIRE(a->mode >= 0 && a->mode <= 2, "bmf_mu_epilogue: bad mode");
     BMF_REQUIRE(a->mode == BMF_MODE_PREPARE || ((a->G || a->den) && a->num), "bmf_mu_epilogue: update modes need num and G (or den)");
     BMF_REQUIRE(!a->num || (a->splits >= 1 && a->slab_stride >= a->rows_pad * a->kp), "bmf_mu_epilogue: bad slab description");
+    BMF_REQUIRE(!a->num || !a->num_block_stride || a->splits == 1, "bmf_mu_epilogue: num in 32-column blocks (num_block_stride) needs splits == 1");
+    BMF_REQUIRE(!a->num || !a->num_block_stride || a->num_block_stride >= a->rows_pad * 32, "bmf_mu_epilogue: num_block_stride must be >= rows_pad * 32");
     BMF_REQUIRE(a->terms >= 0 && a->terms <= 3, "bmf_mu_epilogue: terms must be 0..3 (0 = no bf16 panel)");
     BMF_REQUIRE(a->ldp >= a->rows_pad && a->ldp % 4 == 0, "bmf_mu_epilogue: ldp must be >= rows_pad and a multiple of 4");
     BMF_REQUIRE(a->ldcb >= a->rows_pad / 32, "bmf_mu_epilogue: ldcb too small");

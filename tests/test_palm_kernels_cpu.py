@@ -190,7 +190,8 @@ FORMS = [("ring", 0.0), ("ring", 0.15), ("ring", 0.9), ("den", 0.0), ("den", 0.1
 def general_cases():
     """Every (k, form) pair once (30 cases), the row shapes, slab counts, variants and advance_prev cycled through them: 7 is coprime
     to the 15 row shapes, so the first 15 cases already reach each of them (test_general_cases_cover_the_grid).  Then two cases with
-    36 blocks, where the ring form permutes its blocks: 32 in all."""
+    36 blocks, where the ring form permutes its blocks (32 of them, and a plain tail of 4), and one with 68, where the block map reaches a
+    round index above 0: 33 in all."""
     cases, i = [], 0
     for form, beta in FORMS:
         for k, kp in K_CASES:
@@ -200,6 +201,7 @@ def general_cases():
             i += 1
     cases.append(dict(form="ring", beta=0.0, k=40, kp=64, rows_pad=4608, rows=4500, splits=3, variant=ELBMF, advance_prev=1, seed=4198))
     cases.append(dict(form="ring", beta=0.15, k=20, kp=32, rows_pad=4608, rows=4481, splits=1, variant=PRIMP, advance_prev=0, seed=4199))
+    cases.append(dict(form="ring", beta=0.15, k=33, kp=64, rows_pad=8704, rows=8650, splits=3, variant=ELBMF, advance_prev=1, seed=4200))
     return cases
 
 
@@ -440,7 +442,9 @@ def test_general_cases_cover_the_grid():
         assert {c["beta"] for c in sub} == {0.0, 0.15} and {c["variant"] for c in sub} == {ELBMF, PRIMP} and {c["advance_prev"] for c in sub} == {0, 1}
     assert any(c["rows_pad"] % 512 == 0 and c["form"] == "ring" and c["kp"] == kp and (c["beta"] != 0) == hb for c in cases
                for kp in (32, 64) for hb in (False, True))
-    assert len({case_id(c) for c in cases}) == len(cases)
+    assert len({case_id(c) for c in cases}) == len(cases) == 33
+    ring_blocks = {c["rows_pad"] // 128 for c in cases if c["form"] == "ring"}      # the permuted block map: one round and a tail; two rounds
+    assert any(32 <= nb < 64 and nb % 32 for nb in ring_blocks) and any(nb >= 64 and nb % 32 for nb in ring_blocks)
 
 
 @pytest.mark.parametrize("c", general_cases(), ids=case_id)
