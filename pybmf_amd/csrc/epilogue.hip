@@ -252,7 +252,12 @@ __global__ __launch_bounds__(256, 2) void mu_epilogue_kernel(bmf_epilogue_args a
 // issued three chunks ahead), which leaves room for the 24 registers of plane segments beside the accumulators at two waves per SIMD.
 // MODE, LIMBS: compile-time (the run-time forms kept the element-wise part full of branches, and the register allocator spilled
 // around them)
-template <int NT, int MODE, int LIMBS>
+//
+// S: the number of numerator slabs, compile-time for 1..3.  The ring then keeps the RAW value of every slab and the element-wise part
+// adds them, ((0 + s0) + s1) + s2, when it consumes the chunk: the slab loads stay in flight three chunks deep like the fp64 ones.
+// S = 0 is the run-time count (any `splits`, or no numerator at all): the slabs are added as they are loaded, in the same order, and
+// every slab then costs the wave one full drain of its load queue per chunk.
+template <int NT, int MODE, int LIMBS, int S>
 __global__ __launch_bounds__(256, 2) void mu_epilogue_i8_kernel(bmf_epilogue_args a) {
 #ifdef BMF_EPI_STAMP
     if (blockIdx.x == 0 && threadIdx.x == 0) { bmf_epi_stamps[0] = __builtin_amdgcn_s_memtime(); bmf_epi_stamps[14] = __builtin_amdgcn_s_memrealtime(); }
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void mu_epilogue_i8_kernel(bmf_epilogue_arg
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) psc[nt] = (double)a.plane_scale[32 * nt + c];
 
-    double reg_acc = 0.0, dot_acc = 0.0;
+    double reg_acc = 0.0, dot_acc = 0.0, d_first = 0.0;
     unsigned colword[NT];
     float cm[NT];
     unsigned seg[3][NT][4];   // [digit][column tile][dword of the 16-byte segment]
@@ -324,7 +329,8 @@ __global__ __launch_bounds__(256, 2) void mu_epilogue_i8_kernel(bmf_epilogue_arg
     const unsigned noff = (unsigned)(4 * h * (int)ld + c);     // ... in the numerator slabs
     // chunk q2 = rows i = 2 q2 + jj, jj = 0, 1  (i & 3 = 2 (q2 & 1) + jj, i >> 2 = q2 >> 1, rl = (i & 3) + 8 (i >> 2) + 4 h)
     constexpr int CR = 2;   // rows of a lane per chunk
-    auto load_chunk = [&](int q2, double (&fv)[CR][NT], float (&nv)[CR][NT]) {
+    constexpr int SR = S > 0 ? S : 1;   // numerator values the ring keeps per element
+    auto load_chunk = [&](int q2, double (&fv)[CR][NT], float (&nv)[CR][NT][SR]) {
 #pragma unroll
         for (int jj = 0; jj < CR; ++jj) {
             const int i = CR * q2 + jj;
@@ -334,21 +340,32 @@ __global__ __launch_bounds__(256, 2) void mu_epilogue_i8_kernel(bmf_epilogue_arg
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 fv[jj][nt] = fq[loff + (i & 3) * KP + 32 * nt];
-                nv[jj][nt] = 0.f;
+                if constexpr (S == 0) nv[jj][nt][0] = 0.f;
             }
         }
-        if (a.num)
+        if constexpr (S > 0) {   // loads only: nothing here waits for data
+#pragma unroll
+            for (int sp = 0; sp < S; ++sp)
+#pragma unroll
+                for (int jj = 0; jj < CR; ++jj) {
+                    const int i = CR * q2 + jj;
+                    const float* nq = a.num + (int64_t)sp * a.slab_stride + (row0 + 8 * (i >> 2)) * ld;
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) nv[jj][nt][sp] = nq[noff + (i & 3) * (int)ld + (int)bs * nt];
+                }
+        } else if (a.num) {
             for (int sp = 0; sp < a.splits; ++sp) {
 #pragma unroll
                 for (int jj = 0; jj < CR; ++jj) {
                     const int i = CR * q2 + jj;
                     const float* nq = a.num + (int64_t)sp * a.slab_stride + (row0 + 8 * (i >> 2)) * ld;
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) nv[jj][nt] += nq[noff + (i & 3) * (int)ld + (int)bs * nt];
+                    for (int nt = 0; nt < NT; ++nt) nv[jj][nt][0] += nq[noff + (i & 3) * (int)ld + (int)bs * nt];
                 }
             }
+        }
     };
-    auto do_chunk = [&](int q2, const double (&fv)[CR][NT], const float (&nv)[CR][NT]) {
+    auto do_chunk = [&](int q2, const double (&fv)[CR][NT], const float (&nv)[CR][NT][SR]) {
 #pragma unroll
         for (int jj = 0; jj < CR; ++jj) {
             const int i = CR * q2 + jj;
@@ -365,7 +382,12 @@ __global__ __launch_bounds__(256, 2) void mu_epilogue_i8_kernel(bmf_epilogue_arg
                 const bool ok = row_ok && col < k;
                 const unsigned eoff = loff + j * KP + 32 * nt;
                 const double f = fv[jj][nt];
-                const float num = nv[jj][nt];
+                float num = nv[jj][nt][0];
+                if constexpr (S > 0) {   // the slabs in ascending order from +0, the sum the run-time form takes at load time
+                    num = 0.f;
+#pragma unroll
+                    for (int sp = 0; sp < S; ++sp) num += nv[jj][nt][sp];
+                }
                 double fn = f;
                 if constexpr (update) {
                     double den = (double)fg[nt][i];
@@ -397,9 +419,28 @@ __global__ __launch_bounds__(256, 2) void mu_epilogue_i8_kernel(bmf_epilogue_arg
                 sq[eoff] = fn32;
                 cm[nt] = fmaxf(cm[nt], fabsf(fn32));
 
-                const double d = fn * fn - fn;
-                reg_acc += d * d;
-                dot_acc += fn * (double)num;
+                if constexpr (!update) {
+                    const double d = fn * fn - fn;
+                    reg_acc += d * d;
+                    dot_acc += fn * (double)num;
+                } else {
+                    // The two block sums with every fused multiply-add written out.  Left to the compiler, the first two terms of
+                    // a sum of products, x0 y0 + x1 y1, may become fma(x1, y1, x0 y0) or fma(x0, y0, x1 y1) -- and it chose per
+                    // instantiation (the forms with a compile-time slab count differently from the run-time one), which moved the
+                    // last bit of `partials`.  Written here is what the kernels have always computed: sum((fn^2 - fn)^2) starts
+                    // from the square of the LAST column tile of the first row, the tiles before it are fused onto that, every
+                    // later element in order; sum(fn num) takes every element in order.
+                    const double d = fma(fn, fn, -fn);
+                    dot_acc = fma(fn, (double)num, dot_acc);
+                    if (i == 0 && nt < NT - 1) {
+                        d_first = d;
+                    } else if (i == 0) {
+                        reg_acc = d * d;
+                        if constexpr (NT == 2) reg_acc = fma(d_first, d_first, reg_acc);
+                    } else {
+                        reg_acc = fma(d, d, reg_acc);
+                    }
+                }
 
                 const bool bit = ok && (fn > (double)a.thr);
                 ball[nt] = __ballot(bit);
@@ -448,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void mu_epilogue_i8_kernel(bmf_epilogue_arg
         // eight dependent memory round trips of ~2 us each under load and the kernel was latency-bound (72 us for U at the
         // headline shape, against 62 + 27 for the two kernels it replaces).  (sched_barriers: the scheduler must not hoist further.)
         double fr[4][CR][NT];
-        float nr[4][CR][NT];
+        float nr[4][CR][NT][SR];
         load_chunk(0, fr[0], nr[0]);
         load_chunk(1, fr[1], nr[1]);
         load_chunk(2, fr[2], nr[2]);
@@ -543,11 +584,18 @@ extern "C" int bmf_mu_epilogue(const bmf_epilogue_args* a, void* stream) {
         BMF_REQUIRE(a->rows_pad % 512 == 0 && a->ldp >= a->rows_pad && a->ldp % 16 == 0 && bmf_aligned16(a->planes),
                     "bmf_mu_epilogue: planes need rows_pad %% 512 == 0, ldp >= rows_pad, ldp %% 16 == 0 and a 16-byte aligned pointer");
         BMF_REQUIRE(!a->den, "bmf_mu_epilogue: planes cannot be combined with a precomputed denominator (den)");
-#define BMF_EPI8_CASE(NT_, M_, L_) \
-    if (a->kp == 32 * NT_ && a->mode == M_ && a->limbs == L_) BMF_LAUNCH((mu_epilogue_i8_kernel<NT_, M_, L_>), grid, block, 0, s, *a);
-        BMF_EPI8_CASE(1, 0, 2) BMF_EPI8_CASE(1, 0, 3) BMF_EPI8_CASE(1, 1, 2) BMF_EPI8_CASE(1, 1, 3) BMF_EPI8_CASE(1, 2, 2) BMF_EPI8_CASE(1, 2, 3)
-        BMF_EPI8_CASE(2, 0, 2) BMF_EPI8_CASE(2, 0, 3) BMF_EPI8_CASE(2, 1, 2) BMF_EPI8_CASE(2, 1, 3) BMF_EPI8_CASE(2, 2, 2) BMF_EPI8_CASE(2, 2, 3)
+        // the update modes (num is required there) with 1..3 slabs take the forms with a compile-time slab count; PREPARE, and any
+        // other count, the run-time form
+        const int sc = (a->mode != BMF_MODE_PREPARE && a->splits <= 3) ? a->splits : 0;
+#define BMF_EPI8_CASE_S(NT_, M_, L_, S_) \
+    if (a->kp == 32 * NT_ && a->mode == M_ && a->limbs == L_ && sc == S_) BMF_LAUNCH((mu_epilogue_i8_kernel<NT_, M_, L_, S_>), grid, block, 0, s, *a);
+#define BMF_EPI8_CASE(NT_, L_) \
+    BMF_EPI8_CASE_S(NT_, 0, L_, 0) \
+    BMF_EPI8_CASE_S(NT_, 1, L_, 0) BMF_EPI8_CASE_S(NT_, 1, L_, 1) BMF_EPI8_CASE_S(NT_, 1, L_, 2) BMF_EPI8_CASE_S(NT_, 1, L_, 3) \
+    BMF_EPI8_CASE_S(NT_, 2, L_, 0) BMF_EPI8_CASE_S(NT_, 2, L_, 1) BMF_EPI8_CASE_S(NT_, 2, L_, 2) BMF_EPI8_CASE_S(NT_, 2, L_, 3)
+        BMF_EPI8_CASE(1, 2) BMF_EPI8_CASE(1, 3) BMF_EPI8_CASE(2, 2) BMF_EPI8_CASE(2, 3)
 #undef BMF_EPI8_CASE
+#undef BMF_EPI8_CASE_S
         BMF_LAUNCH_CHECK();
         return BMF_OK;
     }
