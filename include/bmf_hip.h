@@ -367,6 +367,11 @@ int bmf_mae_sum_ex(const uint32_t* XTbits, int64_t ldxt, int64_t m_pad, int64_t 
 int bmf_mae_sum_tiled(const uint32_t* XTtiled, int64_t ldxt, int64_t m_pad, int64_t n_pad, const float* U, const float* V, int kp,
                       uint16_t* ws, double* sum, void* stream);
 
+/* The grid bmf_mae_sum / _ex / _tiled launch at this shape on the current device (it depends on the compute-unit count): the
+ * n_pad / 64 stages of 64 columns are cut into `groups` column ranges of `stages_per_group` stages (the last may be shorter); the
+ * m_pad / 256 row blocks are dealt to the 8 XCDs in runs of ceil(row_blocks / 8). */
+int bmf_mae_plan(int64_t m_pad, int64_t n_pad, int* groups, int* stages_per_group);
+
 /* ---- Boolean cover count ------------------------------------------------------------------------------------ */
 
 /* counts[0] += TP = sum X and pd, counts[1] += FP = sum (not X) and pd, with pd[i][j] = OR_l ubits[i][l] & V_l[j]
@@ -401,6 +406,11 @@ int bmf_real_product(const float* U, int64_t m_pad, int32_t m, const float* V, i
 int bmf_residual_sums(const uint32_t* Xbits, int64_t m_pad, int64_t ldx, int32_t m, int32_t n, const float* U,
                       const float* V, int kp, double* sums, const int32_t* stop, void* stream);
 
+/* The grid bmf_residual_sums, bmf_residual_sums_f32, bmf_thresh_eval and bmf_real_product launch for an m x n problem (host
+ * arithmetic only): ceil(m / 128) row blocks x `col_groups` column groups, each a run of `tiles_per_group` 32-column tiles (the last
+ * group may be shorter). */
+int bmf_residual_plan(int64_t m, int64_t n, int* col_groups, int* tiles_per_group);
+
 /* out[0] += sum_i W[i] (A[i] - B[i])^2 over n elements of dense fp64 arrays (W may be NULL = all ones): twice the reference's
  * rec_error(X_gt, X_pd, W) = 0.5 * sum(multiply(W, power(X_gt - X_pd, 2))) (models/BinaryMFPenalty.py:175-179) for a caller that
  * hands in an explicit prediction X_pd instead of factors (PNLPF's error() does, models/PNLPF.py:1,50-58).  Block partials added
@@ -420,6 +430,9 @@ int bmf_frag_rows_f32(const float* V, int64_t rows_pad, int kp, float* frag, voi
  * what sums holds (the caller zeroes it). */
 int bmf_residual_sums_f32_tiled(const float* Xtiled, int64_t m_pad, int64_t n_pad, const float* U, const float* Vfrag, int kp,
                                 double* sums, void* stream);
+/* The grid of that pass (host arithmetic only): m_pad / 64 row tiles x `splits` column splits of `stages_per_split` 64-column
+ * stages (the last may be shorter). */
+int bmf_residual_tiled_plan(int64_t m_pad, int64_t n_pad, int* splits, int* stages_per_split);
 
 /* ---- whole-iteration driver (BinaryMFPenalty._fit loop body, models/BinaryMFPenalty.py:81-115) ---------------- */
 

@@ -185,10 +185,12 @@ SIGNATURES = {
     "bmf_mae_sum": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "bmf_mae_sum_ex": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "bmf_mae_sum_tiled": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "bmf_mae_plan": (C.c_int, [_i64, _i64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmf_cover_count": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
     "bmf_boolean_product_bits": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _i64, _vp, _i64, _vp]),
     "bmf_real_product": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, C.c_int, _vp, _i64, _vp]),
     "bmf_residual_sums": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "bmf_residual_plan": (C.c_int, [_i64, _i64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmf_sqdiff_work": (_i64, []),
     "bmf_sqdiff_sum": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "bmf_residual_sums_f32": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, C.c_int, _vp, _vp]),
@@ -225,6 +227,7 @@ SIGNATURES = {
     "bmf_xf_f32_tiled_bf3": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, C.c_int, _vp]),
     "bmf_xf_f32_tiled_resid_bf3": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),
     "bmf_residual_sums_f32_tiled": (C.c_int, [_vp, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp]),
+    "bmf_residual_tiled_plan": (C.c_int, [_i64, _i64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmf_wnmf_real_prepare": (C.c_int, [C.POINTER(WnmfRealState), _vp]),
     "bmf_wnmf_real_run": (C.c_int, [C.POINTER(WnmfRealState), _i32, _i32, _i32, _vp]),
     "bmf_thresh_eval64_work": (_i64, [_i64, _i64, C.c_int]),

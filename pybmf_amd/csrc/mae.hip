@@ -207,6 +207,10 @@ __global__ __launch_bounds__(WAVES * 64) void mae_kernel(const uint32_t* __restr
     };
     // X^T row j = 16 jt + c of the stage, the two words that cover this wave's rows i0 .. i0 + 63
     const unsigned x_addr = lds0 + (unsigned)(NADD * 64 * ROWB + c * 32 + wave * 8);
+    // The pair a ds_read_b64 is filling is tied to its wait as ONE 64-bit operand ("+v"(x[jt])), never half by half: tied as
+    // .x and .y, the compiler moved a half into a register of its own with a v_mov placed BEFORE the s_waitcnt (register copies are
+    // not ordered against the asm statements), i.e. it copied the old contents whenever the read had not landed yet -- one launch
+    // in twenty of the kp = 32 single-product pass was a few cells off.
     auto load_xw = [&](unsigned slot_off, uint2 (&x)[4]) {
         const unsigned addr = x_addr + slot_off;
 #pragma unroll
@@ -314,7 +318,7 @@ __global__ __launch_bounds__(WAVES * 64) void mae_kernel(const uint32_t* __restr
     load_xw(0u, xw);
     wait_b(b0h, b0l);
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt) { asm volatile("" : "+v"(xw[jt].x)); asm volatile("" : "+v"(xw[jt].y)); }
+    for (int jt = 0; jt < 4; ++jt) asm volatile("" : "+v"(xw[jt]));   // the whole pair as ONE operand: see load_xw
     __builtin_amdgcn_sched_barrier(0);
     int slot = 0;  // ring slot of stage s
     for (int s = s0; s < s1; ++s) {
@@ -339,8 +343,7 @@ __global__ __launch_bounds__(WAVES * 64) void mae_kernel(const uint32_t* __restr
         BMF_MAE_PHASE(off1, 0, b0h, b0l, b1h, b1l, pb, xw[3], pa)
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {   // landed with that phase's wait; the copy must not move above it
-            asm volatile("" : "+v"(xwn[jt].x));
-            asm volatile("" : "+v"(xwn[jt].y));
+            asm volatile("" : "+v"(xwn[jt]));
             xw[jt] = xwn[jt];
         }
         total += (double)acc_abs;  // keep the fp32 partial short: one stage = 64 cells per lane
@@ -547,7 +550,7 @@ __global__ __launch_bounds__(256) void mae32_kernel(const uint32_t* __restrict__
     _Pragma("unroll") for (int st = 0; st < 8; ++st) {                                                \
         if (st == 4 && (WAIT_AT_HALF)) {                                                              \
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                        \
-            asm volatile("" : "+v"(XNEXT.x), "+v"(XNEXT.y));                                          \
+            asm volatile("" : "+v"(XNEXT));                                                           \
         }                                                                                             \
         BMF_M32_VALU(if (st < 4) add8(IDLE, st); else init8(IDLE, XNEXT, st - 4);)                    \
         __builtin_amdgcn_sched_barrier(0);                                                            \
@@ -576,7 +579,7 @@ __global__ __launch_bounds__(256) void mae32_kernel(const uint32_t* __restrict__
     load_xw(0u, xw);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     tie_b(bA);
-    asm volatile("" : "+v"(xw[0].x), "+v"(xw[0].y), "+v"(xw[1].x), "+v"(xw[1].y));
+    asm volatile("" : "+v"(xw[0]), "+v"(xw[1]));
 #pragma unroll
     for (int i = 0; i < 16; ++i) { pb[0][i] = 0.f; pb[1][i] = 0.f; }
 #pragma unroll
@@ -613,7 +616,7 @@ __global__ __launch_bounds__(256) void mae32_kernel(const uint32_t* __restrict__
         BMF_MAE32_PHASE(pb, bB, pa, xwn[0], true)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         tie_b(bA);
-        asm volatile("" : "+v"(xwn[1].x), "+v"(xwn[1].y));
+        asm volatile("" : "+v"(xwn[1]));
         xw[1] = xwn[1];
         total += (double)acc0 + (double)acc1;   // keep the fp32 partials short: one stage = 64 cells per lane
         acc0 = 0.f;
@@ -724,6 +727,30 @@ __global__ __launch_bounds__(256) void resid_wide_f64_kernel(const uint32_t* __r
 
 }  // namespace
 
+// Grid of the MAE kernels: workgroups of 256 rows of U (row blocks, dealt to the 8 XCDs in runs of rb_per_xcd) x column ranges of
+// `per` 64-column stages: about six workgroups per resident slot (2 per CU), so that the last round is short.  One rule for both
+// launchers below and for bmf_mae_plan.
+static void mae_plan(int64_t m_pad, int64_t n_pad, int* row_blocks, int* rb_per_xcd, int* groups, int* per) {
+    const int rb = (int)(m_pad / 256), stages = (int)(n_pad / 64);
+    int g = (6 * 2 * bmf_cu_count() + rb - 1) / rb;
+    if (g > stages) g = stages;
+    if (g < 1) g = 1;
+    const int p = (stages + g - 1) / g;
+    *row_blocks = rb;
+    *rb_per_xcd = (rb + 7) / 8;
+    *groups = (stages + p - 1) / p;
+    *per = p;
+}
+
+extern "C" int bmf_mae_plan(int64_t m_pad, int64_t n_pad, int* groups, int* stages_per_group) {
+    BMF_REQUIRE(groups && stages_per_group, "bmf_mae_plan: null pointer");
+    BMF_REQUIRE(m_pad > 0 && m_pad % 256 == 0 && n_pad > 0 && n_pad % 64 == 0 && m_pad <= INT32_MAX && n_pad <= INT32_MAX,
+                "bmf_mae_plan: m_pad must be a positive multiple of 256, n_pad of 64");
+    int row_blocks, rb_per_xcd;
+    mae_plan(m_pad, n_pad, &row_blocks, &rb_per_xcd, groups, stages_per_group);
+    return BMF_OK;
+}
+
 // sums[0] += sum |X - U V^T|, sums[1] += sum (X - U V^T)^2 for factors of two 64-column blocks each (64 < k <= 128).  By size, as
 // bmf_mae_launch: the single-product fp16 pass at K = 128 from 2^24 padded cells up (the per-cell error averages out over the sum),
 // resid_wide_f64_kernel below that (ws unused).  ws: (m_pad + n_pad) * 128 uint16.
@@ -747,13 +774,8 @@ int bmf_mae_wide_launch(const uint32_t* XT, int64_t ldxt, int64_t m_pad, int64_t
     auto blocks = [](int64_t rows) { const int64_t b = (rows * 32 + 255) / 256; return (unsigned)(b < 2048 ? b : 2048); };
     BMF_LAUNCH(to_f16_wide_kernel, dim3(blocks(m_pad)), dim3(256), 0, s, UA, UB, m_pad, -X_ONE, Uh);
     BMF_LAUNCH(to_f16_wide_kernel, dim3(blocks(n_pad)), dim3(256), 0, s, VA, VB, n_pad, 1.0f, Vh);
-    const int row_blocks = (int)(m_pad / 256), stages = (int)(n_pad / 64);
-    const int rb_per_xcd = (row_blocks + 7) / 8;
-    int groups = (6 * 2 * bmf_cu_count() + row_blocks - 1) / row_blocks;
-    if (groups > stages) groups = stages;
-    if (groups < 1) groups = 1;
-    const int per = (stages + groups - 1) / groups;
-    groups = (stages + per - 1) / per;
+    int row_blocks, rb_per_xcd, groups, per;
+    mae_plan(m_pad, n_pad, &row_blocks, &rb_per_xcd, &groups, &per);
     dim3 grid((unsigned)(8 * rb_per_xcd * groups)), block(256);
     if (x_tiled) BMF_LAUNCH((mae32_kernel<128, true, true>), grid, block, 0, s, XT, ldxt, n_pad, Uh, Vh, row_blocks, rb_per_xcd, per, sums, nullptr);
     else BMF_LAUNCH((mae32_kernel<128, false, true>), grid, block, 0, s, XT, ldxt, n_pad, Uh, Vh, row_blocks, rb_per_xcd, per, sums, nullptr);
@@ -791,14 +813,8 @@ int bmf_mae_launch(const uint32_t* XTbits, int64_t ldxt, int64_t m_pad, int64_t 
     // CU: measured 886 vs 686 us)
     // 4 waves = 256 rows of U per workgroup, two workgroups per CU.  8 waves / 512 rows (one workgroup per CU, the same two
     // waves per SIMD) halve the V traffic from L2 but tie eight waves to every stage barrier: 0.75 vs 0.69 ms.
-    const int row_blocks = (int)(m_pad / 256), stages = (int)(n_pad / 64);
-    const int rb_per_xcd = (row_blocks + 7) / 8;
-    // column ranges: about six workgroups per resident slot (2 per CU), so that the last round is short
-    int groups = (6 * 2 * bmf_cu_count() + row_blocks - 1) / row_blocks;
-    if (groups > stages) groups = stages;
-    if (groups < 1) groups = 1;
-    const int per = (stages + groups - 1) / groups;
-    groups = (stages + per - 1) / per;
+    int row_blocks, rb_per_xcd, groups, per;
+    mae_plan(m_pad, n_pad, &row_blocks, &rb_per_xcd, &groups, &per);
     dim3 grid((unsigned)(8 * rb_per_xcd * groups)), block(256);
     if (one) {   // (one fp16 product per cell: the 32x32x16 form, mae32_kernel; the 16x16 form it replaced lost its switch in round 5)
         if (kp == 32 && x_tiled) BMF_LAUNCH((mae32_kernel<32, true>), grid, block, 0, s, XTbits, ldxt, n_pad, Uh, Vh, row_blocks, rb_per_xcd, per, sum, stop);

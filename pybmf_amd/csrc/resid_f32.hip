@@ -175,6 +175,27 @@ extern "C" int bmf_frag_rows_f32(const float* V, int64_t rows_pad, int kp, float
     return bmf_frag_rows_f32_launch(V, rows_pad, kp, frag, nullptr, (hipStream_t)stream);
 }
 
+// Grid of the tiled pass: row tiles of 64 x column splits of `sps` 64-column stages: ~1024 workgroups, at least ~8 stages each.
+// One rule for the launcher and for bmf_residual_tiled_plan.
+static void residual_tiled_plan(int64_t m_pad, int64_t n_pad, int* tiles, int* splits, int* sps) {
+    const int t = (int)(m_pad / 64), stages = (int)(n_pad / 64);
+    int sp = (1024 + t - 1) / t;
+    if (sp > stages / 8) sp = stages / 8 > 0 ? stages / 8 : 1;
+    const int per = (stages + sp - 1) / sp;
+    *tiles = t;
+    *splits = (stages + per - 1) / per;
+    *sps = per;
+}
+
+extern "C" int bmf_residual_tiled_plan(int64_t m_pad, int64_t n_pad, int* splits, int* stages_per_split) {
+    BMF_REQUIRE(splits && stages_per_split, "bmf_residual_tiled_plan: null pointer");
+    BMF_REQUIRE(m_pad > 0 && m_pad % 64 == 0 && n_pad > 0 && n_pad % 64 == 0 && m_pad <= INT32_MAX && n_pad <= INT32_MAX,
+                "bmf_residual_tiled_plan: m_pad and n_pad must be positive multiples of 64");
+    int tiles;
+    residual_tiled_plan(m_pad, n_pad, &tiles, splits, stages_per_split);
+    return BMF_OK;
+}
+
 /* Xtiled: bmf_tile_f32 of the zero-padded m_pad x n_pad X (both multiples of 64); Vfrag: bmf_frag_rows_f32 of V (n_pad x kp).
  * sums[0..1] are ADDED to (zeroed by the caller). */
 int bmf_residual_tiled_launch(const float* Xtiled, int64_t m_pad, int64_t n_pad, const float* U, const float* Vfrag, int kp, double* sums,
@@ -184,11 +205,9 @@ int bmf_residual_tiled_launch(const float* Xtiled, int64_t m_pad, int64_t n_pad,
     BMF_REQUIRE(m_pad > 0 && m_pad % 64 == 0 && n_pad > 0 && n_pad % 64 == 0, "bmf_residual_sums_f32_tiled: m_pad and n_pad must be positive multiples of 64");
     BMF_REQUIRE(kp == 32 || kp == 64, "bmf_residual_sums_f32_tiled: kp must be 32 or 64");
     BMF_REQUIRE(bmf_aligned16(Xtiled) && bmf_aligned16(U) && bmf_aligned16(V), "bmf_residual_sums_f32_tiled: pointers must be 16-byte aligned");
-    const int tiles = (int)(m_pad / 64), stages = (int)(n_pad / 64);
-    int splits = (1024 + tiles - 1) / tiles;                 // ~1024 workgroups, at least ~8 stages each
-    if (splits > stages / 8) splits = stages / 8 > 0 ? stages / 8 : 1;
-    const int sps = (stages + splits - 1) / splits;
-    splits = (stages + sps - 1) / sps;
+    const int stages = (int)(n_pad / 64);
+    int tiles, splits, sps;
+    residual_tiled_plan(m_pad, n_pad, &tiles, &splits, &sps);
     dim3 grid((unsigned)(tiles * splits)), block(256);
     if (kp == 32) BMF_LAUNCH(resid_f32_ring_kernel<32>, grid, block, 0, s, Xtiled, stages, sps, U, V, sums, tiles, stop);
     else BMF_LAUNCH(resid_f32_ring_kernel<64>, grid, block, 0, s, Xtiled, stages, sps, U, V, sums, tiles, stop);

@@ -172,12 +172,15 @@ __global__ __launch_bounds__(256) void thresh_transform_kernel(const float* __re
         const int j = (int)(i - r * kp);
         float s = 0.f, d = 0.f;
         if (r < rows && j < k) {
+            // from e = exp(-|z|) <= 1 on both sides, as sigmoid_pair of thresh64.hip: 1 - sg cancels for z > 0 (d was 17 % off at
+            // z = 35 and 0 from z = 36.8 on, where lam exp(-z) is still an ordinary fp32 number)
             const double z = ((double)F[i] - x) * lam;
-            double sg;
-            if (z >= 0) sg = 1.0 / (1.0 + exp(-z));
-            else { const double e = exp(z); sg = e / (1.0 + e); }
+            const double e = exp(-fabs(z));
+            double sg, dg;
+            if (z >= 0) { sg = 1.0 / (1.0 + e); dg = lam * e * sg * sg; }
+            else { sg = e / (1.0 + e); dg = lam * sg / (1.0 + e); }
             s = (float)sg;
-            d = (float)(lam * sg * (1.0 - sg));
+            d = (float)dg;
         }
         S[i] = s;
         if (D) D[i] = d;
@@ -186,16 +189,32 @@ __global__ __launch_bounds__(256) void thresh_transform_kernel(const float* __re
 
 }  // namespace
 
+// Grid of the residual / product kernels: row blocks of 128 rows (4 waves x 32) x column groups, each group a contiguous run of
+// `per` 32-column tiles.  Enough workgroups to fill the chip ~4x.  One rule for every launcher here and for bmf_residual_plan.
+static void residual_plan(int64_t m, int64_t n, int* row_blocks, int* col_groups, int* per) {
+    const int rb = (int)((m + 127) / 128);
+    const int col_tiles = (int)((n + 31) / 32);
+    int groups = (1024 + rb - 1) / rb;
+    if (groups > col_tiles) groups = col_tiles;
+    if (groups < 1) groups = 1;
+    const int p = (col_tiles + groups - 1) / groups;
+    *row_blocks = rb;
+    *col_groups = (col_tiles + p - 1) / p;
+    *per = p;
+}
+
+extern "C" int bmf_residual_plan(int64_t m, int64_t n, int* col_groups, int* tiles_per_group) {
+    BMF_REQUIRE(col_groups && tiles_per_group, "bmf_residual_plan: null pointer");
+    BMF_REQUIRE(m >= 1 && n >= 1 && m <= INT32_MAX && n <= INT32_MAX, "bmf_residual_plan: m and n must be positive int32 values");
+    int row_blocks;
+    residual_plan(m, n, &row_blocks, col_groups, tiles_per_group);
+    return BMF_OK;
+}
+
 int bmf_residual_launch(const uint32_t* Xbits, int64_t m_pad, int64_t ldx, int m, int n, const float* A, const float* B,
                         const float* dA, const float* dB, int kp, double* sums, const int32_t* stop, hipStream_t s) {
-    const int row_blocks = (int)((m + 127) / 128);  // 4 waves x 32 rows
-    const int col_tiles = (n + 31) / 32;
-    // enough blocks to fill the chip ~4x; each block walks a contiguous range of column tiles
-    int col_groups = (1024 + row_blocks - 1) / row_blocks;
-    if (col_groups > col_tiles) col_groups = col_tiles;
-    if (col_groups < 1) col_groups = 1;
-    const int per = (col_tiles + col_groups - 1) / col_groups;
-    col_groups = (col_tiles + per - 1) / per;
+    int row_blocks, col_groups, per;
+    residual_plan(m, n, &row_blocks, &col_groups, &per);
     dim3 grid((unsigned)row_blocks, (unsigned)col_groups), block(256);
     const bool grad = dA != nullptr;
     if (kp == 32) {
@@ -253,12 +272,8 @@ int bmf_residual_launch_f32(const float* X, int64_t m_pad, int64_t ldx, int m, i
     BMF_REQUIRE(ldx >= n && ldx % 32 == 0, "bmf_residual_sums_f32: ldx must be a multiple of 32 covering n");
     BMF_REQUIRE(kp == 32 || kp == 64, "bmf_residual_sums_f32: kp must be 32 or 64");
     BMF_REQUIRE(bmf_aligned16(X) && bmf_aligned16(U) && bmf_aligned16(V), "bmf_residual_sums_f32: pointers must be 16-byte aligned");
-    const int row_blocks = (int)((m + 127) / 128);
-    const int col_tiles = (n + 31) / 32;
-    int col_groups = (1024 + row_blocks - 1) / row_blocks;
-    if (col_groups > col_tiles) col_groups = col_tiles;
-    const int per = (col_tiles + col_groups - 1) / col_groups;
-    col_groups = (col_tiles + per - 1) / per;
+    int row_blocks, col_groups, per;
+    residual_plan(m, n, &row_blocks, &col_groups, &per);
     dim3 grid((unsigned)row_blocks, (unsigned)col_groups), block(256);
     const uint32_t* Xw = reinterpret_cast<const uint32_t*>(X);
     if (kp == 32)
@@ -281,12 +296,8 @@ extern "C" int bmf_real_product(const float* U, int64_t m_pad, int32_t m, const 
     BMF_REQUIRE(kp == 32 || kp == 64, "bmf_real_product: kp must be 32 or 64");
     BMF_REQUIRE(ldo >= n, "bmf_real_product: ldo < n");
     BMF_REQUIRE(bmf_aligned16(U) && bmf_aligned16(V), "bmf_real_product: factors must be 16-byte aligned");
-    const int row_blocks = (int)((m + 127) / 128);
-    const int col_tiles = (n + 31) / 32;
-    int col_groups = (1024 + row_blocks - 1) / row_blocks;
-    if (col_groups > col_tiles) col_groups = col_tiles;
-    const int per = (col_tiles + col_groups - 1) / col_groups;
-    col_groups = (col_tiles + per - 1) / per;
+    int row_blocks, col_groups, per;
+    residual_plan(m, n, &row_blocks, &col_groups, &per);
     dim3 grid((unsigned)row_blocks, (unsigned)col_groups), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (kp == 32) BMF_LAUNCH(product_kernel<32>, grid, block, 0, s, U, V, m, n, per, out, ldo);

@@ -81,6 +81,18 @@ int main(void) {
     EXPECT_REFUSED(bmf_masked_thresh64(NULL, NULL, NULL, NULL, NULL, NULL, 1, NULL, NULL, NULL, NULL, 32, NULL, 1, NULL, NULL));
     EXPECT_REFUSED(bmf_masked_thresh64_k(NULL, NULL, NULL, NULL, NULL, NULL, 1, NULL, NULL, NULL, NULL, 32, 16, NULL, 1, NULL, NULL));
     if (bmf_thresh_eval64_work(100, 64, 32) >= 0) ++fails;
+    {   /* the launch-plan queries: refused calls, and the two host-only ones answered (their results land in host ints) */
+        int pa = -7, pb = -7;
+        EXPECT_REFUSED(bmf_residual_plan(130, 70, NULL, &pb));
+        EXPECT_REFUSED(bmf_residual_plan(0, 70, &pa, &pb));
+        EXPECT_REFUSED(bmf_residual_tiled_plan(64, 64, &pa, NULL));
+        EXPECT_REFUSED(bmf_residual_tiled_plan(100, 64, &pa, &pb));
+        EXPECT_REFUSED(bmf_mae_plan(256, 64, NULL, NULL));
+        EXPECT_REFUSED(bmf_mae_plan(255, 64, &pa, &pb));
+        if (pa != -7 || pb != -7) ++fails;
+        if (bmf_residual_plan(128, 32769, &pa, &pb) != 0 || pa != 513 || pb != 2) ++fails;
+        if (bmf_residual_tiled_plan(64, 64 * 17, &pa, &pb) != 0 || pa != 2 || pb != 9) ++fails;
+    }
     EXPECT_REFUSED(bmf_link_pass(NULL, 512, 4, 1, 1, NULL, NULL, 512, 32, 1, 10.0, NULL, NULL, 512 * 32, 1, NULL));
     EXPECT_REFUSED(bmf_link_split(NULL, 512, 32, NULL, NULL));
     EXPECT_REFUSED(bmf_link_pass16(NULL, 512, 4, 1, 1, NULL, NULL, 512, 32, 1, 10.0, NULL, NULL, 512 * 32, 1, NULL));

@@ -65,6 +65,56 @@ def test_bad_arguments_are_refused_without_a_gpu():
     assert lib.bmf_panel_pos(128) == -1
 
 
+def test_host_only_launch_plan_queries():
+    """bmf_residual_plan and bmf_residual_tiled_plan are host arithmetic: bad arguments are refused, and the grids are the ones worked
+    out by hand from the rules in their launchers (csrc/residual.hip, csrc/resid_f32.hip)."""
+    from pybmf_amd import _lib as L
+    lib = L.lib
+    a, b = C.c_int(-7), C.c_int(-7)
+
+    def plan(fn, x, y):
+        a.value = b.value = -7
+        assert fn(x, y, C.byref(a), C.byref(b)) == 0, lib.bmf_last_error()
+        return a.value, b.value
+
+    for fn, name, good in ((lib.bmf_residual_plan, b"bmf_residual_plan", (130, 70)), (lib.bmf_residual_tiled_plan, b"bmf_residual_tiled_plan", (64, 64))):
+        assert fn(good[0], good[1], None, C.byref(b)) == -1 and name + b": null pointer" in lib.bmf_last_error()
+        assert fn(good[0], good[1], C.byref(a), None) == -1 and name in lib.bmf_last_error()
+        for bad in ((0, good[1]), (good[0], 0), (-64, good[1]), (good[0], -64), (1 << 31, good[1]), (good[0], 1 << 31)):
+            a.value = b.value = -7
+            assert fn(bad[0], bad[1], C.byref(a), C.byref(b)) == -1 and name in lib.bmf_last_error(), bad
+            assert (a.value, b.value) == (-7, -7)                      # a refused call writes nothing
+    for bad in ((100, 64), (64, 100), (63, 64), (64, 32)):
+        assert lib.bmf_residual_tiled_plan(bad[0], bad[1], C.byref(a), C.byref(b)) == -1
+    # residual: ceil(m / 128) row blocks; groups = min(ceil(1024 / row blocks), tiles); per = ceil(tiles / groups); groups = ceil(tiles / per)
+    assert plan(lib.bmf_residual_plan, 1, 1) == (1, 1)
+    assert plan(lib.bmf_residual_plan, 130, 70) == (3, 1)             # 2 row blocks -> up to 512 groups; 3 tiles, one each
+    assert plan(lib.bmf_residual_plan, 1000, 333) == (11, 1)          # the largest shape of test_residual_sums: still one tile per group
+    assert plan(lib.bmf_residual_plan, 128, 32768) == (1024, 1)       # 1 row block, 1024 tiles: the last shape with one tile per group
+    assert plan(lib.bmf_residual_plan, 128, 32769) == (513, 2)        # 1025 tiles: 2 per group, 512 full groups and one of 1
+    assert plan(lib.bmf_residual_plan, 129, 32769) == (342, 3)        # 2 row blocks -> 512 groups: 3 per group, 341 full groups and one of 2
+    assert plan(lib.bmf_residual_plan, 8192, 33 * 32 - 5) == (11, 3)  # 64 row blocks -> 16 groups; 33 tiles: 3 per group, 11 full groups
+    assert plan(lib.bmf_residual_plan, 8192, 34 * 32 - 5) == (12, 3)  # 34 tiles: 11 full groups and one of 1
+    assert plan(lib.bmf_residual_plan, 100000, 20000) == (2, 313)     # 782 row blocks -> 2 groups of 313 tiles (625 tiles)
+    # tiled: m_pad / 64 tiles; splits = min(ceil(1024 / tiles), max(stages / 8, 1)); per = ceil(stages / splits); splits = ceil(stages / per)
+    assert plan(lib.bmf_residual_tiled_plan, 64, 64) == (1, 1)
+    assert plan(lib.bmf_residual_tiled_plan, 64, 64 * 15) == (1, 15)
+    assert plan(lib.bmf_residual_tiled_plan, 64, 64 * 17) == (2, 9)   # two splits, 9 + 8 stages
+    assert plan(lib.bmf_residual_tiled_plan, 192, 64 * 23) == (2, 12)
+    assert plan(lib.bmf_residual_tiled_plan, 384, 1024) == (2, 8)     # the shape of test_tiled_real_matrix_kernels: two full splits
+    assert plan(lib.bmf_residual_tiled_plan, 64 * 2048, 64 * 64) == (1, 64)   # 2048 tiles fill the chip: one split
+    assert plan(lib.bmf_residual_tiled_plan, 64 * 100, 64 * 1000) == (11, 91)  # ceil(1024 / 100) = 11 splits of 91 (the last 90)
+    # bmf_mae_plan needs the compute-unit count, so only its argument checks run here
+    assert lib.bmf_mae_plan(256, 64, None, C.byref(b)) == -1 and b"bmf_mae_plan: null pointer" in lib.bmf_last_error()
+    for bad in ((0, 64), (255, 64), (256, 0), (256, 65), (-256, 64), (1 << 32, 64)):
+        assert lib.bmf_mae_plan(bad[0], bad[1], C.byref(a), C.byref(b)) == -1 and b"bmf_mae_plan" in lib.bmf_last_error(), bad
+    import objective_ref as R
+    for m, n in ((1, 1), (130, 70), (128, 65606), (8192, 1083), (100000, 20000), (20, 33000)):
+        assert plan(lib.bmf_residual_plan, m, n) == R.residual_plan(m, n)
+    for mp, np_ in ((64, 64), (192, 64 * 23), (384, 1024), (6400, 64000)):
+        assert plan(lib.bmf_residual_tiled_plan, mp, np_) == R.tiled_plan(mp, np_)
+
+
 def test_no_cpu_fallback():
     """Without a GPU the product refuses to run instead of computing on the host."""
     import torch
