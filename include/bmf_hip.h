@@ -721,7 +721,7 @@ int bmf_faststep_eval(const double* B, const uint32_t* Xbits, const uint32_t* Wb
  *   j < 0: the column is rec[1] read on the device (rec of bmf_concept_scan), and nothing is written when that is -1.
  * bmf_concept_apply: for every c with bit c of v set: Xrs_t[c] &= ~u, Xpd_t[c] |= u;  colcount[c] = |Xrs_t[c]| for all c < n,
  *   *rsum = their sum.  u == v == NULL: only the counts.
- * bmf_bits_confusion: counts[0] = |P & G|, counts[1] = |P| over `rows` rows of ldw words; work: 2 * rows int32. */
+ * bmf_bits_confusion (csrc/bits_common.hip): counts[0] = |P & G|, counts[1] = |P| over `rows` rows of ldw words; work: 2 * rows int32. */
 int64_t bmf_concept_scan_work(int32_t ncand);
 int bmf_concept_scan(const uint32_t* Xt, const uint32_t* Xrs_t, int32_t n, int64_t ldw, const uint32_t* best_u, const int32_t* cand,
                      int32_t ncand, int64_t best_score, void* work, int64_t* score, int32_t* nu, int32_t* nv, int64_t* rec,
@@ -738,7 +738,7 @@ int bmf_bits_confusion(const uint32_t* Pbits, const uint32_t* Gbits, int32_t row
  * padded (axis 0: the transposed matrices, bit row j = column j of X, ld = m_pad / 32; axis 1: the row-major ones).  rs = residual,
  * x = data, pd = cover.  Exact integers; the one fp64 decision is (double)count > t * (double)|a|; no atomics.
  *
- * bmf_mebf_scores: score[j] = |R_j| for j < N;  out[0] = their sum, out[1] = the number of positive scores.
+ * bmf_mebf_scores (csrc/bits_common.hip): score[j] = |R_j| for j < N;  out[0] = their sum, out[1] = the number of positive scores.
  * bmf_mebf_select: weak == 0: rec[0] = the index at rank P / 2 of the P positive scores under (score descending, index descending),
  *   -1 when P = 0; rec[1] = P.  weak != 0 (N >= 2): rec[0], rec[1] = the indices at ranks 0 and 1 of all scores.  rec[2..7] = 0.
  * bmf_mebf_weak_a: a (ld words) = rs[rec[0]] & rs[rec[1]].

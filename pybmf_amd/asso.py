@@ -21,35 +21,27 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr
+from .bitset import BitSetEngine
 from .engine import BitMatrix
-from .grecond import pack_bits, unpack_bits  # noqa: F401  (the packed-word helpers are shared)
 
 WORK_BYTES = 64 << 20   # default ceiling of the (row tile, candidate) partial sums of one launch
 
 
-class AssoEngine:
+class AssoEngine(BitSetEngine):
+    title = "Asso"
+
     def __init__(self, bits: BitMatrix, extra: dict = None):
-        """bits: the training matrix.  extra: {name: BitMatrix} of further ground truths of the same shape (val / test)."""
-        self.bits, self.m, self.n = bits, bits.m, bits.n
-        self.device = dev = bits.device
+        super().__init__(bits, extra)
+        dev = self.device
         self.ldx, self.W = bits.ldx, bits.ldxt
-        self.truth = {"train": bits}
-        for name, B in (extra or {}).items():
-            if (B.m, B.n, B.device) != (bits.m, bits.n, bits.device):
-                raise ValueError(f"the {name} matrix must have the shape and the device of X")
-            self.truth[name] = B
         self._tiles = -(-self.m // 64)
         # candidates per launch: all of them while the partial sums stay within WORK_BYTES, never fewer than 64
         self._max_block = max(64, min(self.n, WORK_BYTES // (16 * self._tiles)))
         n_work = int(lib.bmf_asso_score_work(self.m, self._max_block))
         with torch.cuda.device(dev):
             # X and X^T are in HBM already (BitMatrix); the prediction and the candidate rows add two row-major bit matrices
-            need = (bits.m_pad + self.n) * self.ldx * 4 + n_work + 16 * self.m + 40 * self.n
-            free_b, _ = torch.cuda.mem_get_info(dev)
-            if need > free_b:
-                raise NotImplementedError(f"Asso on {self.m} x {self.n}: the bits of the prediction and of the candidates and the partial "
-                                          f"sums take {need / 2 ** 30:.2f} GiB, {free_b / 2 ** 30:.2f} GiB of device memory are free; "
-                                          "row sharding is not built")
+            self._require_free((bits.m_pad + self.n) * self.ldx * 4 + n_work + 16 * self.m + 40 * self.n,
+                               "the bits of the prediction and of the candidates and the partial sums take", "; row sharding is not built")
             self.pd = torch.zeros_like(bits.bits)
             self.basis = torch.zeros((self.n, self.ldx), dtype=torch.int32, device=dev)
             self._count = torch.zeros(self.n, dtype=torch.int32, device=dev)
@@ -64,19 +56,12 @@ class AssoEngine:
             self._u = torch.zeros(self.W, dtype=torch.int32, device=dev)
             self._v = torch.zeros(self.ldx, dtype=torch.int32, device=dev)
             self._col_work = torch.zeros(-(-self.m // 32), dtype=torch.int32, device=dev)
-            self._conf_work = torch.zeros(2 * self.m, dtype=torch.int32, device=dev)
-            self._conf = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._stream_obj = torch.cuda.current_stream()
-        self._stream = C.c_void_p(self._stream_obj.cuda_stream)
-        self._p_tp, self._p_fp = C.c_void_p(self._rows.data_ptr()), C.c_void_p(self._rows.data_ptr() + 4 * self.m)
+        self._p_tp, self._p_fp = self._p(self._rows), self._p(self._rows, self.m)
         self.list = np.zeros(0, dtype=np.int32)    # the remaining candidates, ascending
         self._rows_fresh = False
         self._weights = None
         self._factors = []
         self.launches = 0                          # of the last best() call
-
-    def _on_stream(self):
-        return torch.cuda.stream(self._stream_obj)
 
     @property
     def n_factors(self) -> int:
@@ -113,7 +98,7 @@ class AssoEngine:
 
     def launch_score(self, pos: int, count: int, best_score: float, w_fp: float, w_fn: float):
         """Enqueue bmf_asso_score and bmf_asso_pick on entries [pos, pos + count) of the device list; no read, no wait."""
-        p_cand = C.c_void_p(self._cand.data_ptr() + 4 * pos)
+        p_cand = self._p(self._cand, pos)
         with torch.cuda.device(self.device), self._on_stream():
             check(lib.bmf_asso_score(ptr(self.bits.bits), ptr(self.pd), ptr(self.basis), self.ldx, self.m, self.n, p_cand, count,
                                      self._p_tp, self._p_fp, w_fp, w_fn, ptr(self._work), self._stream), "bmf_asso_score")
@@ -207,26 +192,5 @@ class AssoEngine:
         for u, v in self._factors:
             self._or_in(u, v)
 
-    def counts(self, name="train"):
-        """(TP, FP, FN, TN) of the prediction bits against data set `name`."""
-        G = self.truth[name]
-        with torch.cuda.device(self.device), self._on_stream():
-            check(lib.bmf_bits_confusion(ptr(self.pd), ptr(G.bits), self.m, self.ldx, ptr(self._conf_work), ptr(self._conf), self._stream),
-                  "bmf_bits_confusion")
-            tp, n_pd = (int(x) for x in self._conf.cpu().numpy())
-        fp, fn = n_pd - tp, int(G.sum_local) - tp
-        return tp, fp, fn, self.m * self.n - tp - fp - fn
-
-    def factor_arrays(self):
-        """(U, V) of the applied factors as uint8 arrays of shape (m, f) and (n, f)."""
-        f = len(self._factors)
-        U, V = np.zeros((self.m, f), dtype=np.uint8), np.zeros((self.n, f), dtype=np.uint8)
-        for i, (u, v) in enumerate(self._factors):
-            U[:, i], V[:, i] = unpack_bits(u, self.m), unpack_bits(v, self.n)
-        return U, V
-
-    def prediction(self):
-        """X_pd as a scipy csr matrix, from the device bits."""
-        from scipy.sparse import csr_matrix
-        b = self.pd[: self.m].cpu().numpy().view(np.uint8)
-        return csr_matrix(np.unpackbits(b, axis=1, bitorder="little")[:, : self.n].astype(int))
+    def _pd_bits(self, for_counts):
+        return self.pd, False

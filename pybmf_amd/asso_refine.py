@@ -17,30 +17,23 @@ least 8 words must fit), optimal_rows k <= 16 (2^k subsets per row); beyond that
 """
 from __future__ import annotations
 
-import ctypes as C
 import struct
 
 import numpy as np
 import torch
 
 from ._lib import check, lib, ptr
+from .bitset import BitSetEngine
 from .engine import BitMatrix
 
 K_MAX_COLUMN, K_MAX_ROWS = 1024, 16
 
 
-class AssoRefineEngine:
+class AssoRefineEngine(BitSetEngine):
     def __init__(self, bits: BitMatrix, extra: dict = None):
-        """bits: the training matrix.  extra: {name: BitMatrix} of further ground truths of the same shape (val / test)."""
-        self.bits, self.m, self.n = bits, bits.m, bits.n
-        self.device = dev = bits.device
+        super().__init__(bits, extra)
+        dev = self.device
         self.ldx = bits.ldx
-        self.sum_x = int(bits.sum_local)
-        self.truth = {"train": bits}
-        for name, B in (extra or {}).items():
-            if (B.m, B.n, B.device) != (bits.m, bits.n, bits.device):
-                raise ValueError(f"the {name} matrix must have the shape and the device of X")
-            self.truth[name] = B
         self.k = 0
         with torch.cuda.device(dev):
             self._part = torch.zeros(3 * self.m, dtype=torch.int64, device=dev)
@@ -48,15 +41,8 @@ class AssoRefineEngine:
             self._j = torch.zeros(self.m, dtype=torch.int32, device=dev)
             self._rec = torch.zeros(4, dtype=torch.int64, device=dev)
             self._rec_host = torch.zeros(4, dtype=torch.int64).pin_memory()
-            self._conf_work = torch.zeros(2 * self.m, dtype=torch.int32, device=dev)
-            self._conf = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._stream_obj = torch.cuda.current_stream()
-        self._stream = C.c_void_p(self._stream_obj.cuda_stream)
         self.pd = None            # the prediction bits, made on demand
         self._pd_fresh = False
-
-    def _on_stream(self):
-        return torch.cuda.stream(self._stream_obj)
 
     # ---- factors ----------------------------------------------------------------------------------------------------------
     def load_factors(self, U, V):
@@ -124,36 +110,19 @@ class AssoRefineEngine:
         return self._j.cpu().numpy().astype(np.int64)
 
     # ---- prediction -----------------------------------------------------------------------------------------------------
-    def _product(self):
-        if self._pd_fresh:
-            return
-        with torch.cuda.device(self.device), self._on_stream():
-            if self.pd is None:
-                self.pd = torch.zeros_like(self.bits.bits)
-            check(lib.bmf_asso_refine_product(ptr(self.U), self.kw, ptr(self.V), self.k, self.ldx, self.m, ptr(self.pd), self._stream),
-                  "bmf_asso_refine_product")
-        self._pd_fresh = True
-
-    def counts(self, name="train"):
-        """(TP, FP, FN, TN) of U o V^T against data set `name`."""
-        G = self.truth[name]
-        self._product()
-        with torch.cuda.device(self.device), self._on_stream():
-            check(lib.bmf_bits_confusion(ptr(self.pd), ptr(G.bits), self.m, self.ldx, ptr(self._conf_work), ptr(self._conf), self._stream),
-                  "bmf_bits_confusion")
-            tp, n_pd = (int(x) for x in self._conf.cpu().numpy())
-        fp, fn = n_pd - tp, int(G.sum_local) - tp
-        return tp, fp, fn, self.m * self.n - tp - fp - fn
+    def _pd_bits(self, for_counts):
+        """U o V^T, built when U has changed since the last product."""
+        if not self._pd_fresh:
+            with torch.cuda.device(self.device), self._on_stream():
+                if self.pd is None:
+                    self.pd = torch.zeros_like(self.bits.bits)
+                check(lib.bmf_asso_refine_product(ptr(self.U), self.kw, ptr(self.V), self.k, self.ldx, self.m, ptr(self.pd), self._stream),
+                      "bmf_asso_refine_product")
+            self._pd_fresh = True
+        return self.pd, False
 
     def factor_arrays(self):
         """(U, V) as uint8 arrays of shape (m, k) and (n, k), from the device bits."""
         U = np.unpackbits(self.U.cpu().numpy().view(np.uint8), axis=1, bitorder="little")[:, : self.k]
         V = np.unpackbits(self.V.cpu().numpy().view(np.uint8), axis=1, bitorder="little")[:, : self.n].T
         return np.ascontiguousarray(U), np.ascontiguousarray(V)
-
-    def prediction(self):
-        """X_pd as a scipy csr matrix, from the device bits."""
-        from scipy.sparse import csr_matrix
-        self._product()
-        b = self.pd[: self.m].cpu().numpy().view(np.uint8)
-        return csr_matrix(np.unpackbits(b, axis=1, bitorder="little")[:, : self.n].astype(int))

@@ -8,7 +8,7 @@
 //
 // asso_basis_kernel    64 x 64 tile of C = X^T X per workgroup, rows of X^T staged in LDS 32 words at a time, a 4 x 4 register tile of
 //                      popcount sums per thread; then bit (i, j) = C[i][j] / C[i][i] > tau in fp64, written as packed words.  C is
-//                      never stored.  asso_rowcount_kernel counts the bits of every row (an empty row is no candidate).
+//                      never stored.  The bits of every row are then counted (bits_common.hip: an empty row is no candidate).
 // asso_score_kernel    64 rows of X x 64 candidates per workgroup.  Per row r and candidate b:
 //                        a = |x_r & ~pd_r & b|,  a + c = |~pd_r & b|;   TP_new = TP_old + a,  FP_new = FP_old + c
 //                      ~pd_r and x_r & ~pd_r are formed once while the row tile is staged; both operands sit in LDS 16 words at a time
@@ -21,7 +21,7 @@
 //                      sweep keeps.
 // asso_column_kernel   the same per-row decision for one candidate, written as the bits of u, and |u|.
 // asso_apply_kernel    PD_r |= v for the rows r of u.
-#include "common.h"
+#include "bits_common.h"
 
 namespace {
 
@@ -109,16 +109,6 @@ __global__ __launch_bounds__(256) void asso_basis_kernel(const uint32_t* __restr
         for (int q = 0; q < 32; ++q) word |= (uint32_t)flag[li][32 * h + q] << q;
         if (i0 + li < n) B[(int64_t)(i0 + li) * ldb + (j0 >> 5) + h] = word;   // (j0 / 32 + h < ldb: n_pad is a multiple of 64)
     }
-}
-
-// count[i] = |B_i|, one wave per row
-__global__ __launch_bounds__(256) void asso_rowcount_kernel(const uint32_t* __restrict__ B, int n, int ldb, int32_t* __restrict__ count) {
-    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    uint32_t c = 0;
-    for (int w = lane; w < ldb; w += 64) c += __popc(B[(int64_t)i * ldb + w]);
-    c = wave_sum(c);
-    if (lane == 0) count[i] = (int32_t)c;
 }
 
 // grid (ceil(ncand / 64), ceil(m / 64)), block 256 = 16 (tx: candidates tx + 16 b) x 16 (ty: rows ty + 16 a).
@@ -320,21 +310,6 @@ __global__ __launch_bounds__(256) void asso_column_kernel(const uint32_t* __rest
     }
 }
 
-// One block: *sum = the n counts added in a fixed order.
-__global__ __launch_bounds__(256) void asso_sum_kernel(const int32_t* __restrict__ x, int n, int64_t* __restrict__ sum) {
-    __shared__ int64_t red[256];
-    const int t = threadIdx.x;
-    int64_t s = 0;
-    for (int i = t; i < n; i += 256) s += x[i];
-    red[t] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) sum[0] = red[0];
-}
-
 // PD_r |= v for every row r whose bit of u is set; one wave per row, 4 rows per block
 __global__ __launch_bounds__(256) void asso_apply_kernel(uint32_t* __restrict__ PD, int ldx, int m, const uint32_t* __restrict__ u,
                                                          const uint32_t* __restrict__ v) {
@@ -356,7 +331,7 @@ extern "C" int bmf_asso_basis(const uint32_t* Xt, int32_t n, int64_t ldw, double
     hipStream_t s = (hipStream_t)stream;
     const unsigned tiles = (unsigned)((n + TILE - 1) / TILE);
     BMF_LAUNCH(asso_basis_kernel, dim3(tiles, tiles), dim3(256), 0, s, Xt, n, (int)ldw, tau, B, (int)ldb);
-    BMF_LAUNCH(asso_rowcount_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, B, n, (int)ldb, count);
+    bits_rowcount_launch(B, n, (int)ldb, count, s);
     BMF_LAUNCH_CHECK();
     return BMF_OK;
 }
@@ -405,7 +380,7 @@ extern "C" int bmf_asso_column(const uint32_t* X, const uint32_t* PD, const uint
     hipStream_t s = (hipStream_t)stream;
     const int words = (m + 31) / 32;   // u: ceil(m / 32) words are written; work: as many int32
     BMF_LAUNCH(asso_column_kernel, dim3((unsigned)words), dim3(256), 0, s, X, PD, b, (int)ldx, m, tp_old, fp_old, w_fp, w_fn, u, work);
-    BMF_LAUNCH(asso_sum_kernel, dim3(1), dim3(256), 0, s, work, words, nu);
+    bits_sum_launch(work, words, nu, nullptr, s);
     BMF_LAUNCH_CHECK();
     return BMF_OK;
 }

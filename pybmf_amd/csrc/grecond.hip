@@ -12,10 +12,10 @@
 // concept_pick_kernel   adds the per-split partial sums in split order and finds the FIRST candidate of the list whose score exceeds
 //                       best_score: the one record the host reads per launch.
 // concept_close_*       best_u &= Xt[j] in place and best_v as a bit vector over the columns, for the accepted candidate only.
-// concept_apply_*       Xrs_t[c] &= ~u, Xpd_t[c] |= u for c in v; then the residual count of every column and their sum.
-// bits_confusion_*      TP = |pd & gt|, |pd| of two bit matrices.
+// concept_apply_*       Xrs_t[c] &= ~u, Xpd_t[c] |= u for c in v; then the residual count of every column and their sum (the sum, and
+//                       the confusion counts of the prediction bits, are in bits_common.hip).
 // Integer adds only, partial sums are added in a fixed order, no atomics: the same input gives the same output whatever the grid.
-#include "common.h"
+#include "bits_common.h"
 
 #include <algorithm>
 
@@ -24,12 +24,6 @@ namespace {
 constexpr int GROUP = 16;      // candidates per workgroup (their u_j share the LDS: GROUP * W words)
 constexpr int WAVES = 4;       // waves per workgroup
 constexpr int MAX_SPLIT = 64;  // column splits of one candidate group
-
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // grid (groups of candidates, column splits), block 256.  LDS: GROUP * W words (dynamic) + the reduction scratch.
 __global__ __launch_bounds__(256) void concept_scan_kernel(const uint32_t* __restrict__ Xt, const uint32_t* __restrict__ Xrs,
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(256) void concept_scan_kernel(const uint32_t* __res
     const uint32_t my_cols = c_first < n ? (uint32_t)((n - c_first + c_step - 1) / c_step) : 0u;
 #pragma unroll
     for (int j = 0; j < GROUP; ++j) {
-        const uint32_t lo = wave_sum_u32(score[j] & 0xffffu), hi = wave_sum_u32(score[j] >> 16);
+        const uint32_t lo = wave_sum(score[j] & 0xffffu), hi = wave_sum(score[j] >> 16);
         if (lane == 0) {
             red_s[wave][j] = (uint64_t)lo + ((uint64_t)hi << 16);
             red_v[wave][j] = (empty >> j & 1u) ? my_cols : nv[j];
@@ -217,42 +211,8 @@ __global__ __launch_bounds__(256) void concept_apply_kernel(uint32_t* __restrict
         }
         cnt += __popc(r);
     }
-    cnt = wave_sum_u32(cnt);
+    cnt = wave_sum(cnt);
     if (lane == 0) colcount[c] = (int32_t)cnt;
-}
-
-// One block: *sum = the n counts added in a fixed order.
-__global__ __launch_bounds__(256) void sum_i32_kernel(const int32_t* __restrict__ x, int n, int64_t* __restrict__ sum) {
-    __shared__ int64_t red[256];
-    const int t = threadIdx.x;
-    int64_t s = 0;
-    for (int i = t; i < n; i += 256) s += x[i];
-    red[t] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) sum[0] = red[0];
-}
-
-// per-row |P & G| and |P| of two bit matrices (one wave per row, 4 rows per block)
-__global__ __launch_bounds__(256) void bits_confusion_kernel(const uint32_t* __restrict__ P, const uint32_t* __restrict__ G, int rows, int W,
-                                                             int32_t* __restrict__ tp, int32_t* __restrict__ np_) {
-    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    uint32_t a = 0, b = 0;
-    for (int w = lane; w < W; w += 64) {
-        const uint32_t p = P[(int64_t)r * W + w];
-        a += __popc(p & G[(int64_t)r * W + w]);
-        b += __popc(p);
-    }
-    a = wave_sum_u32(a);
-    b = wave_sum_u32(b);
-    if (lane == 0) {
-        tp[r] = (int32_t)a;
-        np_[r] = (int32_t)b;
-    }
 }
 
 int scan_splits(int ncand, int n) {
@@ -310,19 +270,7 @@ extern "C" int bmf_concept_apply(uint32_t* Xrs_t, uint32_t* Xpd_t, int32_t n, in
     BMF_REQUIRE(n >= 1 && ldw >= 1, "bmf_concept_apply: need n, ldw >= 1");
     hipStream_t s = (hipStream_t)stream;
     BMF_LAUNCH(concept_apply_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, Xrs_t, Xpd_t, u, v, n, (int)ldw, colcount);
-    BMF_LAUNCH(sum_i32_kernel, dim3(1), dim3(256), 0, s, colcount, n, rsum);
-    BMF_LAUNCH_CHECK();
-    return BMF_OK;
-}
-
-extern "C" int bmf_bits_confusion(const uint32_t* Pbits, const uint32_t* Gbits, int32_t rows, int64_t ldw, int32_t* work, int64_t* counts,
-                                  void* stream) {
-    BMF_REQUIRE(Pbits && Gbits && work && counts, "bmf_bits_confusion: null pointer");
-    BMF_REQUIRE(rows >= 1 && ldw >= 1, "bmf_bits_confusion: need rows, ldw >= 1");
-    hipStream_t s = (hipStream_t)stream;
-    BMF_LAUNCH(bits_confusion_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, Pbits, Gbits, rows, (int)ldw, work, work + rows);
-    BMF_LAUNCH(sum_i32_kernel, dim3(1), dim3(256), 0, s, work, rows, counts);
-    BMF_LAUNCH(sum_i32_kernel, dim3(1), dim3(256), 0, s, work + rows, rows, counts + 1);
+    bits_sum_launch(colcount, n, rsum, nullptr, s);
     BMF_LAUNCH_CHECK();
     return BMF_OK;
 }

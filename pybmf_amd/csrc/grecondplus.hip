@@ -14,19 +14,11 @@
 //   prune    the rows of u_exp whose cells over v are all ones of X covered twice leave u and u_exp, their counts over v drop by one;
 //            then the columns of v_exp likewise over the rows u held BEFORE the row pass           (overlap_rows_kernel, overlap_cols_kernel)
 // Integer adds in a fixed order; the only atomics clear single bits of a word that several lines share.
-#include "common.h"
+#include "bits_common.h"
 
 namespace {
 
 constexpr int STEP_THREADS = 1024;
-
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ inline int popc4(uint4 v) { return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w); }
 
 // One wave per line, 4 lines per block, 16-byte loads.
 __global__ __launch_bounds__(256) void expand_counts_kernel(const uint4* __restrict__ X, const uint4* __restrict__ RS, int lines, int ld4,
@@ -43,9 +35,9 @@ __global__ __launch_bounds__(256) void expand_counts_kernel(const uint4* __restr
         cb += popc4(make_uint4(x.x & (r.x | sv.x), x.y & (r.y | sv.y), x.z & (r.z | sv.z), x.w & (r.w | sv.w)));
         cc += popc4(make_uint4(sv.x & ~x.x, sv.y & ~x.y, sv.z & ~x.z, sv.w & ~x.w));
     }
-    ca = wave_sum_u32(ca);
-    cb = wave_sum_u32(cb);
-    cc = wave_sum_u32(cc);
+    ca = wave_sum(ca);
+    cb = wave_sum(cb);
+    cc = wave_sum(cc);
     if (lane == 0) {
         a[l] = (int32_t)ca;
         b[l] = (int32_t)cb;
@@ -189,23 +181,8 @@ __global__ __launch_bounds__(256) void bits_rebuild_kernel(const uint32_t* __res
             cnt += __popc(r);
         }
     }
-    cnt = wave_sum_u32(cnt);
+    cnt = wave_sum(cnt);
     if (lane == 0 && count) count[l] = (int32_t)cnt;
-}
-
-// One block: *sum = the n counts added in a fixed order.
-__global__ __launch_bounds__(256) void rebuild_sum_kernel(const int32_t* __restrict__ x, int n, int64_t* __restrict__ sum) {
-    __shared__ int64_t red[256];
-    const int t = threadIdx.x;
-    int64_t s = 0;
-    for (int i = t; i < n; i += 256) s += x[i];
-    red[t] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) sum[0] = red[0];
 }
 
 // One wave per pair, 4 per block.  A pair outside the matrices is flagged 0.
@@ -269,10 +246,6 @@ __global__ __launch_bounds__(256) void overlap_cols_kernel(const uint32_t* __res
     }
 }
 
-bool ld_ok(int64_t ld) { return ld >= 4 && ld % 4 == 0 && ld <= (1 << 26); }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 
 extern "C" int bmf_expand_counts(const uint32_t* X, const uint32_t* RS, int32_t lines, int64_t ld, const uint32_t* s, int32_t* abc,
@@ -319,7 +292,7 @@ extern "C" int bmf_bits_rebuild(const uint32_t* X, int32_t lines, int64_t ld, co
     BMF_REQUIRE(aligned4(count) && aligned8(sum), "bmf_bits_rebuild: count must be 4-byte, sum 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     BMF_LAUNCH(bits_rebuild_kernel, dim3((unsigned)((lines + 3) / 4)), dim3(256), 0, st, X, lines, (int)ld, S, M, (int)ldm, f, PD, RS, count);
-    if (sum) BMF_LAUNCH(rebuild_sum_kernel, dim3(1), dim3(256), 0, st, count, lines, sum);
+    if (sum) bits_sum_launch(count, lines, sum, nullptr, st);
     BMF_LAUNCH_CHECK();
     return BMF_OK;
 }

@@ -4,7 +4,7 @@
 // A growth along one axis only touches the bit matrices of ONE orientation: N bit rows of ld words, zero padded.  Axis 0 takes the
 // transposed matrices (bit row j = column j of X, ld = m_pad / 32), axis 1 the row-major ones.  With rs the residual, x the data and
 // pd the cover in that orientation:
-//   score_j = |rs_j|                          (mebf_rowcount_kernel; refreshed by apply for the rows it changed)
+//   score_j = |rs_j|                          (bmf_mebf_scores, bits_common.hip; refreshed by apply for the rows it changed)
 //   mid     = the index at rank P / 2 of the P positive scores under (score descending, index descending)      (mebf_select_kernel)
 //   a       = rs_mid, or rs_first & rs_second for the weak signal                                             (mebf_take_a_kernel)
 //   c_j     = |rs_j & a|,  b_j = (double)c_j > t * (double)|a|,  and for the rows of b only
@@ -14,63 +14,15 @@
 // cover of the factors it kept; otherwise x & ~pd = rs and dTP = sum of c_j over b.
 // mebf_apply_kernel: for the bit rows named by `hit`: rs_j &= ~mask, pd_j |= mask, and their new |rs_j|, |pd_j|.
 // Integer adds in a fixed order, no atomics: the same input gives the same output whatever the grid.
-#include "common.h"
+#include "bits_common.h"
 
 namespace {
 
 constexpr int SEL_THREADS = 1024;
 
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ inline int popc4(uint4 v) { return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w); }
-__device__ inline uint4 and4(uint4 a, uint4 b) { return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w); }
-__device__ inline uint4 andn4(uint4 a, uint4 b) { return make_uint4(a.x & ~b.x, a.y & ~b.y, a.z & ~b.z, a.w & ~b.w); }
-
-// One wave per bit row, 4 rows per block: score[j] = |R_j|.
-__global__ __launch_bounds__(256) void mebf_rowcount_kernel(const uint32_t* __restrict__ R, int N, int ld, int32_t* __restrict__ score) {
-    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= N) return;
-    const uint32_t* r = R + (int64_t)j * ld;
-    uint32_t c = 0;
-    for (int w = lane; w < ld; w += 64) c += __popc(r[w]);
-    c = wave_sum_u32(c);
-    if (lane == 0) score[j] = (int32_t)c;
-}
-
-// One block: out[0] = sum of x, out[1] = number of positive x (out[1] is skipped when want_pos == 0).
-__global__ __launch_bounds__(256) void mebf_sum_kernel(const int32_t* __restrict__ x, int N, int want_pos, int64_t* __restrict__ out) {
-    __shared__ int64_t red[256];
-    __shared__ int32_t pos[256];
-    const int t = threadIdx.x;
-    int64_t s = 0;
-    int32_t p = 0;
-    for (int i = t; i < N; i += 256) {
-        s += x[i];
-        p += x[i] > 0;
-    }
-    red[t] = s;
-    pos[t] = p;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) {
-            red[t] += red[t + o];
-            pos[t] += pos[t + o];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        out[0] = red[0];
-        if (want_pos) out[1] = pos[0];
-    }
-}
-
 // the block's sum / maximum of v, the same in every thread (red: 16 ints of LDS)
 __device__ inline int block_sum(int v, int* red) {
-    v = (int)wave_sum_u32((uint32_t)v);
+    v = (int)wave_sum((uint32_t)v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     int s = 0;
@@ -187,8 +139,8 @@ __global__ __launch_bounds__(256) void mebf_grow_kernel(const uint4* __restrict_
         c += popc4(and4(rs[base + w], av));
         na += popc4(av);
     }
-    c = wave_sum_u32(c);
-    na = wave_sum_u32(na);
+    c = wave_sum(c);
+    na = wave_sum(na);
     const bool in = (double)c > t * (double)na;          // (wave-uniform)
     uint32_t p = 0, q = 0;
     if (in) {
@@ -198,8 +150,8 @@ __global__ __launch_bounds__(256) void mebf_grow_kernel(const uint4* __restrict_
             p += popc4(and4(free_a, xv));
             q += popc4(andn4(free_a, xv));
         }
-        p = wave_sum_u32(p);
-        q = wave_sum_u32(q);
+        p = wave_sum(p);
+        q = wave_sum(q);
     }
     if (lane == 0) {
         cnt[j] = (int32_t)c;
@@ -277,8 +229,8 @@ __global__ __launch_bounds__(256) void mebf_apply_kernel(uint32_t* __restrict__ 
         cr += __popc(rv);
         cp += __popc(pv);
     }
-    cr = wave_sum_u32(cr);
-    cp = wave_sum_u32(cp);
+    cr = wave_sum(cr);
+    cp = wave_sum(cp);
     if (lane == 0) {
         score[j] = (int32_t)cr;
         pdcount[j] = (int32_t)cp;
@@ -286,16 +238,6 @@ __global__ __launch_bounds__(256) void mebf_apply_kernel(uint32_t* __restrict__ 
 }
 
 }  // namespace
-
-extern "C" int bmf_mebf_scores(const uint32_t* R, int32_t N, int64_t ld, int32_t* score, int64_t* out, void* stream) {
-    BMF_REQUIRE(R && score && out, "bmf_mebf_scores: null pointer");
-    BMF_REQUIRE(N >= 1 && ld >= 1 && ld <= (1 << 26), "bmf_mebf_scores: need N >= 1 and 1 <= ld <= 2^26");
-    hipStream_t s = (hipStream_t)stream;
-    BMF_LAUNCH(mebf_rowcount_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, R, N, (int)ld, score);
-    BMF_LAUNCH(mebf_sum_kernel, dim3(1), dim3(256), 0, s, score, N, 1, out);
-    BMF_LAUNCH_CHECK();
-    return BMF_OK;
-}
 
 extern "C" int bmf_mebf_select(const int32_t* score, int32_t N, int32_t weak, int64_t* rec, void* stream) {
     BMF_REQUIRE(score && rec, "bmf_mebf_select: null pointer");
@@ -322,7 +264,7 @@ extern "C" int64_t bmf_mebf_grow_work(int32_t N) {
 extern "C" int bmf_mebf_grow(const uint32_t* rs, const uint32_t* x, const uint32_t* pd, int32_t N, int64_t ld, uint32_t* a,
                              int32_t a_from_rec, double t, void* work, uint32_t* b, int32_t nbw, int64_t* rec, void* stream) {
     BMF_REQUIRE(rs && x && pd && a && work && b && rec, "bmf_mebf_grow: null pointer");
-    BMF_REQUIRE(N >= 1 && ld >= 4 && ld % 4 == 0 && ld <= (1 << 26), "bmf_mebf_grow: need N >= 1 and ld a multiple of 4 words, at most 2^26");
+    BMF_REQUIRE(N >= 1 && ld_ok(ld), "bmf_mebf_grow: need N >= 1 and ld a multiple of 4 words, at most 2^26");
     BMF_REQUIRE((int64_t)nbw * 32 >= N, "bmf_mebf_grow: b needs at least ceil(N / 32) words");
     BMF_REQUIRE(bmf_aligned16(rs) && bmf_aligned16(x) && bmf_aligned16(pd) && bmf_aligned16(a), "bmf_mebf_grow: rs, x, pd and a must be 16-byte aligned");
     BMF_REQUIRE((reinterpret_cast<uintptr_t>(work) & 3u) == 0, "bmf_mebf_grow: work must be 4-byte aligned");
@@ -343,8 +285,8 @@ extern "C" int bmf_mebf_apply(uint32_t* rs, uint32_t* pd, int32_t N, int64_t ld,
     BMF_REQUIRE(N >= 1 && ld >= 1 && ld <= (1 << 26), "bmf_mebf_apply: need N >= 1 and 1 <= ld <= 2^26");
     hipStream_t s = (hipStream_t)stream;
     BMF_LAUNCH(mebf_apply_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, rs, pd, N, (int)ld, hit, mask, score, pdcount);
-    BMF_LAUNCH(mebf_sum_kernel, dim3(1), dim3(256), 0, s, score, N, 0, out);
-    BMF_LAUNCH(mebf_sum_kernel, dim3(1), dim3(256), 0, s, pdcount, N, 0, out + 1);
+    bits_sum_launch(score, N, out, nullptr, s);
+    bits_sum_launch(pdcount, N, out + 1, nullptr, s);
     BMF_LAUNCH_CHECK();
     return BMF_OK;
 }

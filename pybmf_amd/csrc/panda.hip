@@ -15,24 +15,15 @@
 //            d = w_model 1 + (w_fn d_fn + w_fp d_fp), rows with d <= 0 join T; their number and the sums of d_fn and d_fp
 //                                                                                  (panda_item_kernel, panda_rows_kernel, panda_join_kernel)
 // Integer adds in a fixed order, no atomics: the same input gives the same output whatever the grid.
-#include "common.h"
+#include "bits_common.h"
 
 namespace {
-
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ inline long long wave_sum_i64(long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
-
-__device__ inline int popc4(uint4 v) { return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w); }
-__device__ inline uint4 and4(uint4 a, uint4 b) { return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w); }
 
 // the block's sum of v in thread 0 (256 threads; red: 256 int64 of LDS); ends with a barrier
 __device__ inline long long block_sum_256(long long v, long long* red) {
@@ -66,7 +57,7 @@ __global__ __launch_bounds__(256) void panda_couples_kernel(const uint32_t* __re
         }
     }
     s = wave_sum_i64(s);
-    cnt = wave_sum_u32(cnt);
+    cnt = wave_sum(cnt);
     if (lane == 0) out[c] = (int64_t)s - (int64_t)cnt;
 }
 
@@ -87,8 +78,8 @@ __global__ __launch_bounds__(256) void panda_count_kernel(const uint4* __restric
             ca += popc4(and4(A[base + w], tv));
             if (B) cb += popc4(and4(B[base + w], tv));
         }
-        ca = wave_sum_u32(ca);
-        cb = wave_sum_u32(cb);
+        ca = wave_sum(ca);
+        cb = wave_sum(cb);
     }
     if (lane == 0) {
         a[i] = (int32_t)ca;
@@ -219,8 +210,8 @@ __global__ __launch_bounds__(256) void panda_rows_kernel(const uint4* __restrict
         cp += popc4(and4(rs[base + w], iv));
         cq += popc4(and4(pd[base + w], iv));
     }
-    cp = wave_sum_u32(cp);
-    cq = wave_sum_u32(cq);
+    cp = wave_sum(cp);
+    cq = wave_sum(cq);
     if (lane == 0) {
         const double d_fn = -(double)cp;
         const double d_fp = n_i - (double)cq + d_fn;
@@ -266,8 +257,6 @@ __global__ __launch_bounds__(256) void panda_join_kernel(int m, int ldt, int n, 
         out[3] = 0;
     }
 }
-
-bool ld_ok(int64_t ld) { return ld >= 4 && ld % 4 == 0 && ld <= (1 << 26); }
 
 }  // namespace
 

@@ -19,49 +19,27 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib as L
 from ._lib import check, lib, ptr
+from .bitset import BitSetEngine, pack_bits, unpack_bits
 from .engine import BitMatrix
 
 MAX_ROWS_PAD = 32256   # the row sets of a candidate group (16 x m_pad / 8 bytes) and 1 KiB of scratch are kept within 64 KiB of LDS
 
 
-def pack_bits(flags, words: int) -> np.ndarray:
-    """A 0 / 1 vector as `words` little-endian uint32 words (bit i of word i // 32), zero padded."""
-    flags = np.asarray(flags).astype(bool).ravel()
-    out = np.zeros(words * 32, dtype=np.uint8)
-    out[: flags.size] = flags
-    return np.packbits(out, bitorder="little").view(np.uint32).copy()
+class ConceptEngine(BitSetEngine):
+    title = "GreConD"
 
-
-def unpack_bits(words, length: int) -> np.ndarray:
-    """The first `length` bits of packed uint32 words as a bool vector."""
-    return np.unpackbits(np.ascontiguousarray(words, dtype=np.uint32).view(np.uint8), bitorder="little")[:length].astype(bool)
-
-
-class ConceptEngine:
     def __init__(self, bits: BitMatrix, extra: dict = None):
-        """bits: the training matrix.  extra: {name: BitMatrix} of further ground truths of the same shape (val / test)."""
-        self.bits, self.m, self.n = bits, bits.m, bits.n
-        self.device = dev = bits.device
+        super().__init__(bits, extra)
+        dev = self.device
         self.W, self.nvw = bits.ldxt, bits.n_pad // 32
-        self.sum_x = int(bits.sum_local)
-        self.truth = {"train": bits}
-        for name, B in (extra or {}).items():
-            if (B.m, B.n, B.device) != (bits.m, bits.n, bits.device):
-                raise ValueError(f"the {name} matrix must have the shape and the device of X")
-            self.truth[name] = B
         if bits.m_pad > MAX_ROWS_PAD:
             raise NotImplementedError(f"GreConD on {self.m} rows: the concept scan keeps the row sets of 16 candidates within 64 KiB of LDS, "
                                       f"at most {MAX_ROWS_PAD} (padded) rows; row sharding is not built")
         n_work = int(lib.bmf_concept_scan_work(self.n))
         with torch.cuda.device(dev):
             # X and X^T are in HBM already (BitMatrix); the residual and the prediction add two transposed copies
-            need = 2 * bits.n_pad * self.W * 4 + n_work + 64 * self.n
-            free_b, _ = torch.cuda.mem_get_info(dev)
-            if need > free_b:
-                raise NotImplementedError(f"GreConD on {self.m} x {self.n}: the bits of the residual and of the prediction take "
-                                          f"{need / 2 ** 30:.2f} GiB, {free_b / 2 ** 30:.2f} GiB of device memory are free")
+            self._require_free(2 * bits.n_pad * self.W * 4 + n_work + 64 * self.n, "the bits of the residual and of the prediction take")
             self.rs_t = bits.bits_t.clone()
             self.pd_t = torch.zeros_like(bits.bits_t)
             self._work = torch.empty(n_work // 8 + 1, dtype=torch.int64, device=dev)
@@ -70,17 +48,12 @@ class ConceptEngine:
             self._nu = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
             self._nv = torch.zeros(max(self.n, 1), dtype=torch.int32, device=dev)
             self._colcount = torch.zeros(bits.n_pad + 2, dtype=torch.int32, device=dev)   # [residual sum (int64) | count per column]
-            self._conf_work = torch.zeros(2 * self.n, dtype=torch.int32, device=dev)
-            self._conf = torch.zeros(2, dtype=torch.int64, device=dev)
             # state: [rec: 8 int64 | best_v: nvw words | best_u: W words] -- what the host reads after a launch, in one copy
             self._state = torch.zeros(16 + self.nvw + self.W, dtype=torch.int32, device=dev)
             self._state_host = torch.zeros(16 + self.nvw + self.W, dtype=torch.int32).pin_memory()
             self._uv_dev = torch.zeros(self.nvw + self.W, dtype=torch.int32, device=dev)
             self._all_rows = torch.from_numpy(pack_bits(np.ones(self.m, dtype=bool), self.W).view(np.int32)).to(dev)
-            self._stream_obj = torch.cuda.current_stream()
-        self._stream = C.c_void_p(self._stream_obj.cuda_stream)
-        base = self._state.data_ptr()
-        self._p_rec, self._p_v, self._p_u = C.c_void_p(base), C.c_void_p(base + 64), C.c_void_p(base + 64 + 4 * self.nvw)
+        self._p_rec, self._p_v, self._p_u = self._p(self._state), self._p(self._state, 16), self._p(self._state, 16 + self.nvw)
         self._state_np = self._state_host.numpy()
         self._factors = []
         self.launches = self.accepted = 0   # of the last concept() call
@@ -89,7 +62,7 @@ class ConceptEngine:
     # ---- residual / prediction ----------------------------------------------------------------------------------------
     def _refresh_counts(self, u_ptr, v_ptr):
         cc = self._colcount
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             check(lib.bmf_concept_apply(ptr(self.rs_t), ptr(self.pd_t), self.n, self.W, u_ptr, v_ptr, C.c_void_p(cc.data_ptr() + 8),
                                         C.c_void_p(cc.data_ptr()), self._stream), "bmf_concept_apply")
             host = cc[: self.n + 2].cpu().numpy()
@@ -100,7 +73,7 @@ class ConceptEngine:
         """The factor (u, v), packed words as concept() returns them, leaves the residual and joins the prediction."""
         u, v = np.ascontiguousarray(u, dtype=np.uint32), np.ascontiguousarray(v, dtype=np.uint32)
         assert u.size == self.W and v.size == self.nvw
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             self._uv_dev.copy_(torch.from_numpy(np.concatenate([v, u]).view(np.int32)))
         base = self._uv_dev.data_ptr()
         self._refresh_counts(C.c_void_p(base + 4 * self.nvw), C.c_void_p(base))
@@ -114,7 +87,7 @@ class ConceptEngine:
         f = U_bits.shape[0]
         assert V_bits.shape[0] == f
         cc = self._colcount
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             self._fac_u = torch.from_numpy(U_bits.view(np.int32)).to(self.device) if f else None
             self._fac_v = torch.from_numpy(V_bits.view(np.int32)).to(self.device) if f else None
             check(lib.bmf_bits_rebuild(ptr(self.bits.bits_t), self.n, self.W, ptr(self._fac_u) if f else None,
@@ -128,29 +101,8 @@ class ConceptEngine:
     def residual_sum(self) -> int:
         return self._rsum
 
-    def counts(self, name="train"):
-        """(TP, FP, FN, TN) of the prediction bits against data set `name`."""
-        G = self.truth[name]
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
-            check(lib.bmf_bits_confusion(ptr(self.pd_t), ptr(G.bits_t), self.n, self.W, ptr(self._conf_work), ptr(self._conf), self._stream),
-                  "bmf_bits_confusion")
-            tp, n_pd = (int(x) for x in self._conf.cpu().numpy())
-        fp, fn = n_pd - tp, int(G.sum_local) - tp
-        return tp, fp, fn, self.m * self.n - tp - fp - fn
-
-    def factor_arrays(self):
-        """(U, V) of the applied factors as uint8 arrays of shape (m, f) and (n, f)."""
-        f = len(self._factors)
-        U, V = np.zeros((self.m, f), dtype=np.uint8), np.zeros((self.n, f), dtype=np.uint8)
-        for i, (u, v) in enumerate(self._factors):
-            U[:, i], V[:, i] = unpack_bits(u, self.m), unpack_bits(v, self.n)
-        return U, V
-
-    def prediction(self):
-        """X_pd as a scipy csr matrix, from the device bits."""
-        from scipy.sparse import csr_matrix
-        b = self.pd_t[: self.n].cpu().numpy().view(np.uint8)
-        return csr_matrix(np.unpackbits(b, axis=1, bitorder="little")[:, : self.m].T.astype(int))
+    def _pd_bits(self, for_counts):
+        return self.pd_t, True
 
     # ---- concept search -----------------------------------------------------------------------------------------------
     def residual_columns(self) -> np.ndarray:
@@ -159,7 +111,7 @@ class ConceptEngine:
 
     def set_search_state(self, best_u=None, cands=None):
         """Start a search by hand (tests, timing): best_u (packed words; None = all rows), best_v empty, `cands` as the sweep's list."""
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             self._state.zero_()
             self._state[16 + self.nvw:] = self._all_rows if best_u is None else \
                 torch.from_numpy(np.ascontiguousarray(best_u, dtype=np.uint32).view(np.int32)).to(self.device)
@@ -168,14 +120,14 @@ class ConceptEngine:
 
     def launch_scan(self, pos: int, count: int, best_score: int):
         """Enqueue bmf_concept_scan on candidates [pos, pos + count) of the list against the device's best_u; no read, no wait."""
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             check(lib.bmf_concept_scan(ptr(self.bits.bits_t), ptr(self.rs_t), self.n, self.W, self._p_u,
                                        C.c_void_p(self._cand.data_ptr() + 4 * pos), count, int(best_score), ptr(self._work), ptr(self._score),
                                        ptr(self._nu), ptr(self._nv), self._p_rec, self._stream), "bmf_concept_scan")
 
     def scan_results(self, count: int):
         """(score, |u_j|, |v_j|) of the last launch_scan over `count` candidates and its record, on the host."""
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             out = [t[:count].cpu().numpy() for t in (self._score, self._nu, self._nv)]
             rec = self._state[:16].cpu().numpy().view(np.int64)[:5]
         return out[0], out[1], out[2], rec
@@ -183,7 +135,7 @@ class ConceptEngine:
     def _launch(self, pos: int, count: int, best_score: int):
         """Scan candidates [pos, pos + count) of the sweep's list, close the winner on the device, read the record."""
         self.launch_scan(pos, count, best_score)
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             check(lib.bmf_concept_close(ptr(self.bits.bits_t), self.n, self.W, -1, self._p_rec, self._p_u, self._p_v, self._stream),
                   "bmf_concept_close")
             self._state_host.copy_(self._state, non_blocking=True)
@@ -203,7 +155,7 @@ class ConceptEngine:
             last = best_score
             j_list = j_rs[~unpack_bits(v_host, self.nvw * 32)[j_rs]] if j_rs.size else j_rs
             if j_list.size:
-                with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+                with torch.cuda.device(self.device), self._on_stream():
                     self._cand[: j_list.size].copy_(torch.from_numpy(np.ascontiguousarray(j_list)))
             pos = 0
             while pos < j_list.size:

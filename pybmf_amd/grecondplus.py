@@ -23,31 +23,19 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr
+from .bitset import bit_positions, popcount
 from .grecond import ConceptEngine
 
-POP8 = np.array([bin(i).count("1") for i in range(256)], dtype=np.int64)
-
-
-def popcount(words) -> int:
-    return int(POP8[np.ascontiguousarray(words, dtype=np.uint32).view(np.uint8)].sum())
-
-
-def bit_positions(words) -> np.ndarray:
-    """The set bits of packed uint32 words, ascending."""
-    return np.nonzero(np.unpackbits(np.ascontiguousarray(words, dtype=np.uint32).view(np.uint8), bitorder="little"))[0].astype(np.int32)
-
-
 class ExpansionEngine(ConceptEngine):
+    title = "GreConD+"
+
     def __init__(self, bits, extra: dict = None):
         super().__init__(bits, extra)
         dev, m, n = self.device, self.m, self.n
         self.ldx = bits.ldx
         with torch.cuda.device(dev):
-            need = bits.m_pad * self.ldx * 4 + 12 * (m + n) + 8 * int(lib.bmf_expand_rec_words(m, n))
-            free_b, _ = torch.cuda.mem_get_info(dev)
-            if need > free_b:
-                raise NotImplementedError(f"GreConD+ on {m} x {n}: the row-major residual and the expansion counters take "
-                                          f"{need / 2 ** 30:.2f} GiB, {free_b / 2 ** 30:.2f} GiB of device memory are free")
+            self._require_free(bits.m_pad * self.ldx * 4 + 12 * (m + n) + 8 * int(lib.bmf_expand_rec_words(m, n)),
+                               "the row-major residual and the expansion counters take")
             self.rs = bits.bits.clone()                                            # the residual row-major; rebuild() keeps it current
             self._row_abc = torch.zeros(3 * m, dtype=torch.int32, device=dev)
             self._col_abc = torch.zeros(3 * n, dtype=torch.int32, device=dev)
@@ -56,9 +44,8 @@ class ExpansionEngine(ConceptEngine):
             self._n_rec = int(lib.bmf_expand_rec_words(m, n))
             self._rec = torch.zeros(self._n_rec, dtype=torch.int64, device=dev)
             self._rec_host = torch.zeros(self._n_rec, dtype=torch.int64).pin_memory()
-        base = self._sets.data_ptr()
-        self._p_su, self._p_sue = C.c_void_p(base), C.c_void_p(base + 4 * self.W)
-        self._p_sv, self._p_sve = C.c_void_p(base + 8 * self.W), C.c_void_p(base + 8 * self.W + 4 * self.nvw)
+        self._p_su, self._p_sue = self._p(self._sets), self._p(self._sets, self.W)
+        self._p_sv, self._p_sve = self._p(self._sets, 2 * self.W), self._p(self._sets, 2 * self.W + self.nvw)
         self.trace = []
         self.host_reads = 0
 
@@ -67,7 +54,7 @@ class ExpansionEngine(ConceptEngine):
         """ConceptEngine.rebuild, and the row-major residual from the same factors."""
         super().rebuild(U_bits, V_bits)
         f = len(self._factors)
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             check(lib.bmf_bits_rebuild(ptr(self.bits.bits), self.m, self.ldx, ptr(self._fac_v) if f else None,
                                        ptr(self._fac_u) if f else None, self.W, f, None, ptr(self.rs), None, None, self._stream),
                   "bmf_bits_rebuild")
@@ -78,7 +65,7 @@ class ExpansionEngine(ConceptEngine):
     # ---- expansion ----------------------------------------------------------------------------------------------------
     def launch_counts(self):
         """Enqueue the two counts passes against the u and v of the device's sets; no read, no wait."""
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             check(lib.bmf_expand_counts(ptr(self.bits.bits), ptr(self.rs), self.m, self.ldx, self._p_sv, ptr(self._row_abc), self._stream),
                   "bmf_expand_counts")
             check(lib.bmf_expand_counts(ptr(self.bits.bits_t), ptr(self.rs_t), self.n, self.W, self._p_su, ptr(self._col_abc), self._stream),
@@ -89,26 +76,26 @@ class ExpansionEngine(ConceptEngine):
         u, v = np.ascontiguousarray(u, dtype=np.uint32), np.ascontiguousarray(v, dtype=np.uint32)
         assert u.size == self.W and v.size == self.nvw
         host = np.concatenate([u, np.zeros(self.W, np.uint32), v, np.zeros(self.nvw, np.uint32)]).view(np.int32)
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             self._sets.copy_(torch.from_numpy(host))
             self._rec.zero_()
         self.launch_counts()
 
     def launch_steps(self, w_fp: float, w_fn: float, steps: int):
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             check(lib.bmf_expand_steps(ptr(self.bits.bits), ptr(self.rs), ptr(self.bits.bits_t), ptr(self.rs_t), self.m, self.n, self.ldx,
                                        self.W, float(w_fp), float(w_fn), int(steps), ptr(self._row_abc), ptr(self._col_abc), self._p_su,
                                        self._p_sv, self._p_sue, self._p_sve, ptr(self._rec), self._stream), "bmf_expand_steps")
 
     def counters(self):
         """((a, b, c) of the rows, (a, b, c) of the columns) as the device holds them now."""
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             r, c = self._row_abc.cpu().numpy(), self._col_abc.cpu().numpy()
         return r.reshape(3, self.m), c.reshape(3, self.n)
 
     def read_record(self):
         """(joins, stopped, [(axis, index, r_score, c_score) per evaluated step]) of the expansion so far."""
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             self._rec_host.copy_(self._rec, non_blocking=True)
             self._stream_obj.synchronize()
         self.host_reads += 1
@@ -120,7 +107,7 @@ class ExpansionEngine(ConceptEngine):
 
     def sets(self):
         """(u, u_exp, v, v_exp) of the device, packed words."""
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             s = self._sets.cpu().numpy().view(np.uint32)
         W, nvw = self.W, self.nvw
         return s[:W].copy(), s[W:2 * W].copy(), s[2 * W:2 * W + nvw].copy(), s[2 * W + nvw:].copy()
@@ -154,7 +141,7 @@ class ExpansionEngine(ConceptEngine):
         pair_line, pair_set = np.concatenate(pair_line), np.concatenate(pair_set)
         if pair_line.size == 0:
             return 0
-        with torch.cuda.device(self.device), torch.cuda.stream(self._stream_obj):
+        with torch.cuda.device(self.device), self._on_stream():
             S = torch.from_numpy(np.ascontiguousarray(sets).view(np.int32)).to(self.device)
             pl, ps = torch.from_numpy(pair_line).to(self.device), torch.from_numpy(pair_set).to(self.device)
             flag = torch.zeros(pair_line.size, dtype=torch.int32, device=self.device)
@@ -177,12 +164,8 @@ class ExpansionEngine(ConceptEngine):
         if passed == 0:
             return U, V, U_exp, V_exp
         m, n, dev = self.m, self.n, self.device
-        with torch.cuda.device(dev), torch.cuda.stream(self._stream_obj):
-            need = 4 * m * n
-            free_b, _ = torch.cuda.mem_get_info(dev)
-            if need > free_b:
-                raise NotImplementedError(f"GreConD+ overlap pruning on {m} x {n}: the count matrix U @ V.T takes {need / 2 ** 30:.2f} GiB, "
-                                          f"{free_b / 2 ** 30:.2f} GiB of device memory are free; tiling it is not built")
+        with torch.cuda.device(dev), self._on_stream():
+            self._require_free(4 * m * n, "the count matrix U @ V.T of the overlap pruning takes", "; tiling it is not built")
             dU, dV = torch.from_numpy(U.view(np.int32)).to(dev), torch.from_numpy(V.view(np.int32)).to(dev)
             dUe, dVe = torch.from_numpy(U_exp.view(np.int32)).to(dev), torch.from_numpy(V_exp.view(np.int32)).to(dev)
             cov = torch.empty((m, n), dtype=torch.int32, device=dev)

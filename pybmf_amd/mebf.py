@@ -20,14 +20,12 @@ and counts against the cover of the second, and the next apply() makes the secon
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from ._lib import check, lib, ptr
+from .bitset import BitSetEngine
 from .engine import BitMatrix
-from .grecond import unpack_bits
 
 
 class _State:
@@ -43,18 +41,13 @@ class _State:
         self.factors = []
 
 
-class MedianEngine:
+class MedianEngine(BitSetEngine):
+    title = "MEBF"
+
     def __init__(self, bits: BitMatrix, extra: dict = None):
-        """bits: the training matrix.  extra: {name: BitMatrix} of further ground truths of the same shape (val / test)."""
-        self.bits, self.m, self.n = bits, bits.m, bits.n
-        self.device = dev = bits.device
+        super().__init__(bits, extra)
+        dev = self.device
         self.W, self.nvw = bits.ldxt, bits.ldx
-        self.sum_x = int(bits.sum_local)
-        self.truth = {"train": bits}
-        for name, B in (extra or {}).items():
-            if (B.m, B.n, B.device) != (bits.m, bits.n, bits.device):
-                raise ValueError(f"the {name} matrix must have the shape and the device of X")
-            self.truth[name] = B
         self.x = [bits.bits_t, bits.bits]
         self.N, self.ld = [self.n, self.m], [self.W, self.nvw]
         self.matrix_bytes = bits.m_pad * bits.n_pad // 8
@@ -74,25 +67,11 @@ class MedianEngine:
             self._wstate_host = torch.zeros_like(self._wstate, device="cpu").pin_memory()
             self._uv_dev = torch.zeros(W + nvw, dtype=torch.int32, device=dev)
             self._out = torch.zeros(4, dtype=torch.int64, device=dev)
-            self._conf_work = torch.zeros(2 * self.n, dtype=torch.int32, device=dev)
-            self._conf = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._stream_obj = torch.cuda.current_stream()
-        self._stream = C.c_void_p(self._stream_obj.cuda_stream)
         self.reads = 0                        # host reads (stream synchronisations) so far
         self._reset(self._live)
 
     def _require(self, matrices, what):
-        need = matrices * self.matrix_bytes
-        free_b, _ = torch.cuda.mem_get_info(self.device)
-        if need > free_b:
-            raise NotImplementedError(f"MEBF on {self.m} x {self.n}: {what} take {need} more bytes ({need / 2 ** 30:.2f} GiB), "
-                                      f"{free_b} bytes of device memory are free; row sharding is not built")
-
-    def _on_stream(self):
-        return torch.cuda.stream(self._stream_obj)
-
-    def _p(self, tensor, word=0):
-        return C.c_void_p(tensor.data_ptr() + 4 * word)
+        self._require_free(matrices * self.matrix_bytes, what + " take", "; row sharding is not built")
 
     # ---- residual / cover ---------------------------------------------------------------------------------------------
     def _reset(self, st):
@@ -171,34 +150,21 @@ class MedianEngine:
         return self._fp_fn(self._kept if self._stale else self._live)
 
     def counts(self, name="train"):
-        """(TP, FP, FN, TN) of the prediction bits against data set `name`."""
-        st = self._live
-        if name == "train":
-            tp = self.sum_x - st.rsum
-            fp, fn = st.pdsum - tp, st.rsum
-        else:
-            G = self.truth[name]
-            with torch.cuda.device(self.device), self._on_stream():
-                check(lib.bmf_bits_confusion(ptr(st.pd[0]), ptr(G.bits_t), self.n, self.W, ptr(self._conf_work), ptr(self._conf), self._stream),
-                      "bmf_bits_confusion")
-                tp, n_pd = (int(x) for x in self._conf.cpu().numpy())
+        """(TP, FP, FN, TN) of the prediction bits against data set `name`; the training set's without a device read."""
+        if name != "train":
             self.reads += 1
-            fp, fn = n_pd - tp, int(G.sum_local) - tp
+            return super().counts(name)
+        fp, fn = self._fp_fn(self._live)
+        tp = self.sum_x - fn
         return tp, fp, fn, self.m * self.n - tp - fp - fn
 
-    def factor_arrays(self):
-        """(U, V) of the factors that make up the prediction, as uint8 arrays of shape (m, f) and (n, f)."""
-        fs = self._live.factors
-        U, V = np.zeros((self.m, len(fs)), dtype=np.uint8), np.zeros((self.n, len(fs)), dtype=np.uint8)
-        for i, (u, v) in enumerate(fs):
-            U[:, i], V[:, i] = unpack_bits(u, self.m), unpack_bits(v, self.n)
-        return U, V
+    def _pd_bits(self, for_counts):
+        return (self._live.pd[0], True) if for_counts else (self._live.pd[1], False)
 
-    def prediction(self):
-        """X_pd as a scipy csr matrix, from the device bits."""
-        from scipy.sparse import csr_matrix
-        b = self._live.pd[1][: self.m].cpu().numpy().view(np.uint8)
-        return csr_matrix(np.unpackbits(b, axis=1, bitorder="little")[:, : self.n].astype(int))
+    @property
+    def _factors(self):
+        """The factors that make up the prediction."""
+        return self._live.factors
 
     def bit_matrices(self, kept=False):
         """(rs_t, pd_t, rs, pd) of the live (or the kept) set as host uint32 arrays (tests)."""

@@ -26,16 +26,14 @@ fit(..., block=N) sets the number of candidates per launch (default: all that re
 from __future__ import annotations
 
 import numpy as np
-from scipy.sparse import lil_matrix
 
-from .BaseModel import BaseModel
-from .ContinuousModel import ContinuousModel
+from .BooleanModel import BooleanModel
 
 METRICS = ['TP', 'TPR', 'FP', 'FPR', 'FN', 'FNR', 'ERR', 'ACC', 'Recall', 'Precision', 'F1']
 
 
-class Asso(BaseModel):
-    device = "cuda:0"
+class Asso(BooleanModel):
+    title = "Asso"
 
     def __init__(self, tau, k=None, tol=0, w_fp=0.5, w_fn=None):
         self.check_params(tau=tau, k=k, tol=tol, w_fp=w_fp, w_fn=w_fn)
@@ -44,38 +42,14 @@ class Asso(BaseModel):
         self._block = kwargs.pop("block", None)
         if kwargs.pop("basis_dim", 1) != 1:
             raise NotImplementedError("Asso builds its candidates from the columns of X (basis_dim=1): the transposed model is not built")
-        if kwargs.get("task", getattr(self, "task", None)) == "prediction":
-            raise NotImplementedError("Asso scores whole matrices (task='reconstruction'): the scorer of stored entries takes factor "
-                                      "panels of at most 128 columns, not the prediction bits this model keeps")
         super().fit(X_train, X_val, X_test, **kwargs)
-        self._engine = self._make_engine()
-        self._counts = {}
-        self.X_pd = None   # built from the device bits on first access
-        self._fit()
-        self.finish(show_logs=self.show_logs, save_model=self.save_model, show_result=self.show_result)
 
-    def _init_factors(self):
-        """lil factors, k columns or one (BaseModelTools.py:275-286 of the reference)."""
-        if hasattr(self, "U") or hasattr(self, "V"):
-            print("[I] U, V existed. Skipping initialization.")
-            return
-        k = self.k if getattr(self, "k", None) is not None else 1
-        self.U, self.V = lil_matrix((self.m, k)), lil_matrix((self.n, k))
-
-    def _make_engine(self):
+    def _engine_class(self):
         from ..asso import AssoEngine
-        from ..engine import BitMatrix
-        for X in (self._X_input, self.X_val, self.X_test):
-            if X is not None and not ContinuousModel._values_are_boolean(X):
-                raise NotImplementedError("Asso takes Boolean (0/1) matrices")
-        bits = BitMatrix(self._X_input, self.device)
-        if bits.max_u8 > 1:
-            raise NotImplementedError("Asso takes Boolean (0/1) matrices")
-        extra = {name: BitMatrix(X, self.device) for name, X in (("val", self.X_val), ("test", self.X_test)) if X is not None}
-        return AssoEngine(bits, extra)
+        return AssoEngine
 
     def _fit(self):
-        from ..asso import unpack_bits
+        from ..bitset import unpack_bits
         eng = self._engine
         w_fp = self.w_fp
         w_fn = 1 - w_fp if self.w_fn is None else self.w_fn
@@ -100,36 +74,18 @@ class Asso(BaseModel):
                 eng.apply(np.zeros_like(u_bits), np.zeros_like(v_bits))
             eng.apply(u_bits, v_bits)
             eng.remove(cand)
-            self._counts, self.X_pd = {}, None
-            tp, fp, fn, tn = self._counts_of("train")
+            self._invalidate()
+            tp, fp, fn, _ = self._counts_of("train")
             score_half = -0.5 * np.float64(fp) + 0.5 * np.float64(tp)
             desc_len = 1 * (self.U.sum() + self.V.sum()) + 1 * np.float64(fp) + 1 * np.float64(fn)
             n_u, n_v = int(u.sum()), int(v.sum())
             self.evaluate(df_name='updates', head_info={'k': k},
                           train_info={'score': best_score, 'score_0.5': score_half, 'desc_len': desc_len, 'shape': [n_u, n_v]},
                           metrics=METRICS, verbose=self.verbose)
-            error = 1 - np.float64(tp + tn) / (self.m * self.n)
+            error = self._train_error()
             print("[I] k: {}, score: {}, error: {:.3f}, shape: [{}, {}]".format(k, best_score, error, n_u, n_v))
             if not self.early_stop(error=error, k=k):
                 eng.truncate(k)                 # U, V lost factor k: so does the prediction
-                self._counts, self.X_pd = {}, None
+                self._invalidate()
             is_improving = self.early_stop(n_factor=k + 1)   # (the reference keeps only this answer)
             k += 1
-
-    # ---- scores --------------------------------------------------------------------------------------------------
-    def _counts_of(self, name):
-        if name not in self._counts:
-            self._counts[name] = self._engine.counts(name)
-        return self._counts[name]
-
-    def _score(self, name, metrics):
-        """Data set `name` against X_pd, from the integer counts of the prediction bits on the device."""
-        if name != "train" and getattr(self, "X_" + name) is None:
-            raise ValueError(f"no {name} data was given to fit()")
-        if any(mt in ("RMSE", "MAE") for mt in metrics):
-            raise NotImplementedError("Asso scores the Boolean metrics only")
-        return ContinuousModel._metric_values(metrics, None, self._counts_of(name))
-
-    def _make_X_pd(self):
-        """U o V^T of the factors that U, V hold, as csr."""
-        return self._engine.prediction()

@@ -27,17 +27,15 @@ from __future__ import annotations
 import numpy as np
 from scipy.sparse import issparse, lil_matrix
 
-from .BaseModel import BaseModel
-from .ContinuousModel import ContinuousModel
+from .BooleanModel import BooleanModel
 
 
 def _dense(F):
     return np.asarray(F.todense()) if issparse(F) else np.asarray(F)
 
 
-class AssoRefiner(BaseModel):
-    """What AssoIter and AssoOpt share: the imported model, the device engine, the scores from its integer counts."""
-    device = "cuda:0"
+class AssoRefiner(BooleanModel):
+    """What AssoIter and AssoOpt share: the imported model and its way into and out of the device engine; they write `_refine`."""
 
     def check_params(self, **kwargs):
         super().check_params(**kwargs)
@@ -49,34 +47,24 @@ class AssoRefiner(BaseModel):
             del self.model
 
     def fit(self, X_train, X_val=None, X_test=None, **kwargs):
-        name = type(self).__name__
-        if kwargs.get("task", getattr(self, "task", None)) == "prediction":
-            raise NotImplementedError(f"{name} scores whole matrices (task='reconstruction')")
         if self.k is None:
-            raise TypeError(f"{name} needs the number of factors of the imported model: its k is None")
+            raise TypeError(f"{self.title} needs the number of factors of the imported model: its k is None")
         super().fit(X_train, X_val, X_test, **kwargs)
+
+    def init_model(self):
+        super().init_model()
         U, V = _dense(self.U), _dense(self.V)
         if U.shape != (self.m, self.k) or V.shape != (self.n, self.k):
             raise ValueError(f"the imported factors have shapes {U.shape}, {V.shape}; X is {self.m} x {self.n} and k = {self.k}")
-        self._engine = self._make_engine()
-        self._engine.load_factors(U, V)
-        self._counts = {}
-        self.X_pd = None   # built from the device bits on first access
-        self._fit()
-        self.U = lil_matrix(self._engine.factor_arrays()[0].astype(np.float64))
-        self.finish(show_logs=self.show_logs, save_model=self.save_model, show_result=self.show_result)
 
-    def _make_engine(self):
+    def _engine_class(self):
         from ..asso_refine import AssoRefineEngine
-        from ..engine import BitMatrix
-        for X in (self._X_input, self.X_val, self.X_test):
-            if X is not None and not ContinuousModel._values_are_boolean(X):
-                raise NotImplementedError(f"{type(self).__name__} takes Boolean (0/1) matrices")
-        bits = BitMatrix(self._X_input, self.device)
-        if bits.max_u8 > 1:
-            raise NotImplementedError(f"{type(self).__name__} takes Boolean (0/1) matrices")
-        extra = {name: BitMatrix(X, self.device) for name, X in (("val", self.X_val), ("test", self.X_test)) if X is not None}
-        return AssoRefineEngine(bits, extra)
+        return AssoRefineEngine
+
+    def _fit(self):
+        self._engine.load_factors(_dense(self.U), _dense(self.V))
+        self._refine()
+        self.U = lil_matrix(self._engine.factor_arrays()[0].astype(np.float64))
 
     def _weights(self):
         return self.w_fp, (1 - self.w_fp if self.w_fn is None else self.w_fn)
@@ -86,30 +74,14 @@ class AssoRefiner(BaseModel):
         tn = self.m * self.n - self._engine.sum_x - fp
         return 1 - np.float64(tp + tn) / (self.m * self.n)
 
-    # ---- scores --------------------------------------------------------------------------------------------------
-    def _counts_of(self, name):
-        if name not in self._counts:
-            self._counts[name] = self._engine.counts(name)
-        return self._counts[name]
-
-    def _score(self, name, metrics):
-        """Data set `name` against X_pd, from the integer counts of the prediction bits on the device."""
-        if name != "train" and getattr(self, "X_" + name) is None:
-            raise ValueError(f"no {name} data was given to fit()")
-        if any(mt in ("RMSE", "MAE") for mt in metrics):
-            raise NotImplementedError(f"{type(self).__name__} scores the Boolean metrics only")
-        return ContinuousModel._metric_values(metrics, None, self._counts_of(name))
-
-    def _make_X_pd(self):
-        """U o V^T as csr, from the device bits."""
-        return self._engine.prediction()
-
 
 class AssoIter(AssoRefiner):
+    title = "AssoIter"
+
     def __init__(self, model, w_fp=0.5, w_fn=None):
         self.check_params(model=model, w_fp=w_fp, w_fn=w_fn)
 
-    def _fit(self):
+    def _refine(self):
         eng = self._engine
         w_fp, w_fn = self._weights()
         tp, fp, _, _ = self._counts_of("train")
@@ -121,7 +93,7 @@ class AssoIter(AssoRefiner):
         while is_improving:
             for k in range(self.k):
                 score, tp, fp, _ = eng.refine_column(k, w_fp, w_fn)      # the column is written whatever the error does
-                self._counts, self.X_pd = {}, None
+                self._invalidate()
                 error = self._error(tp, fp)
                 self.visits.append((k, float(error), bool(error < best_error)))
                 if error < best_error:

@@ -25,6 +25,8 @@ from .AssoIter import AssoRefiner
 
 
 class AssoOpt(AssoRefiner):
+    title = "AssoOpt"
+
     def __init__(self, model, w_fp=1, w_fn=1):
         self.check_params(model=model, w_fp=w_fp, w_fn=w_fn)
 
@@ -34,13 +36,13 @@ class AssoOpt(AssoRefiner):
             raise NotImplementedError(f"k = {self.k}: AssoOpt searches 2^k subsets per row, k <= {K_MAX_ROWS}")
         super().fit(X_train, X_val, X_test, **kwargs)
 
-    def _fit(self):
+    def _refine(self):
         w_fp, w_fn = self._weights()
         tic = time.perf_counter()
         _, tp, fp, _ = self._engine.optimal_rows(w_fp, w_fn)
         toc = time.perf_counter()
         print("[I] Exhaustive search finished in {}s.".format(toc - tic))
         self.chosen = self._engine.chosen()
-        self._counts, self.X_pd = {}, None
+        self._invalidate()
         score = -w_fp * np.float64(fp) + w_fn * np.float64(tp)
         self.evaluate(df_name='refinements', train_info={'score': score})

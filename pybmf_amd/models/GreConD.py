@@ -23,52 +23,26 @@ the same result.
 from __future__ import annotations
 
 import numpy as np
-from scipy.sparse import lil_matrix
 
-from .BaseModel import BaseModel
-from .ContinuousModel import ContinuousModel
+from .BooleanModel import BooleanModel
 
 
-class GreConD(BaseModel):
-    device = "cuda:0"
+class GreConD(BooleanModel):
+    title = "GreConD"
 
     def __init__(self, k=None, tol=0):
         self.check_params(k=k, tol=tol)
 
     def fit(self, X_train, X_val=None, X_test=None, **kwargs):
         self._block = kwargs.pop("block", None)
-        if kwargs.get("task", getattr(self, "task", None)) == "prediction":
-            raise NotImplementedError("GreConD scores whole matrices (task='reconstruction'): the scorer of stored entries takes factor "
-                                      "panels of at most 128 columns, not the prediction bits this model keeps")
         super().fit(X_train, X_val, X_test, **kwargs)
-        self._engine = self._make_engine()
-        self._counts = {}
-        self.X_pd = None   # built from the device bits on first access
-        self._fit()
-        self.finish(show_logs=self.show_logs, save_model=self.save_model, show_result=self.show_result)
 
-    def _init_factors(self):
-        """lil factors, k columns or one (BaseModelTools.py:275-286 of the reference)."""
-        if hasattr(self, "U") or hasattr(self, "V"):
-            print("[I] U, V existed. Skipping initialization.")
-            return
-        k = self.k if getattr(self, "k", None) is not None else 1
-        self.U, self.V = lil_matrix((self.m, k)), lil_matrix((self.n, k))
-
-    def _make_engine(self):
-        from ..engine import BitMatrix
+    def _engine_class(self):
         from ..grecond import ConceptEngine
-        for X in (self._X_input, self.X_val, self.X_test):
-            if X is not None and not ContinuousModel._values_are_boolean(X):
-                raise NotImplementedError("GreConD takes Boolean (0/1) matrices")
-        bits = BitMatrix(self._X_input, self.device)
-        if bits.max_u8 > 1:
-            raise NotImplementedError("GreConD takes Boolean (0/1) matrices")
-        extra = {name: BitMatrix(X, self.device) for name, X in (("val", self.X_val), ("test", self.X_test)) if X is not None}
-        return ConceptEngine(bits, extra)
+        return ConceptEngine
 
     def _fit(self):
-        from ..grecond import unpack_bits
+        from ..bitset import unpack_bits
         eng = self._engine
         k = 0
         is_factorizing = True
@@ -80,29 +54,10 @@ class GreConD(BaseModel):
             u, v = unpack_bits(u_bits, self.m), unpack_bits(v_bits, self.n)
             self.set_factors(k, u=u.astype(np.float64)[:, None], v=v.astype(np.float64)[:, None])
             eng.apply(u_bits, v_bits)
-            self._counts, self.X_pd = {}, None
+            self._invalidate()
             n_u, n_v = int(u.sum()), int(v.sum())
             self.evaluate(df_name='updates', head_info={'k': k, 'score': score, 'shape': [n_u, n_v]})
-            tp, fp, fn, tn = self._counts_of("train")
-            error = 1 - np.float64(tp + tn) / (self.m * self.n)
+            error = self._train_error()
             print("[I] k: {}, score: {}, error: {:.3f}, shape: [{}, {}]".format(k, score, error, n_u, n_v))
             is_factorizing = self.early_stop(error=error, n_factor=k + 1, k=k)
             k += 1
-
-    # ---- scores --------------------------------------------------------------------------------------------------
-    def _counts_of(self, name):
-        if name not in self._counts:
-            self._counts[name] = self._engine.counts(name)
-        return self._counts[name]
-
-    def _score(self, name, metrics):
-        """Data set `name` against X_pd, from the integer counts of the prediction bits on the device."""
-        if name != "train" and getattr(self, "X_" + name) is None:
-            raise ValueError(f"no {name} data was given to fit()")
-        if any(mt in ("RMSE", "MAE") for mt in metrics):
-            raise NotImplementedError("GreConD scores the Boolean metrics only")
-        return ContinuousModel._metric_values(metrics, None, self._counts_of(name))
-
-    def _make_X_pd(self):
-        """U o V^T of every factor that was applied (the one a tolerance stop truncated included), as csr."""
-        return self._engine.prediction()

@@ -43,6 +43,8 @@ def _inside(a, b) -> bool:
 
 
 class GreConDPlus(GreConD):
+    title = "GreConD+"
+
     def __init__(self, k=None, tol=0, w_fp=0.5, w_fn=None):
         if w_fp is None:
             raise ValueError("w_fp must be a finite number")
@@ -66,25 +68,16 @@ class GreConDPlus(GreConD):
             self.__dict__.pop(name, None)
         super().fit(X_train, X_val, X_test, **kwargs)
 
-    def _make_engine(self):
-        from ..engine import BitMatrix
+    def _engine_class(self):
         from ..grecondplus import ExpansionEngine
-        from .ContinuousModel import ContinuousModel
-        for X in (self._X_input, self.X_val, self.X_test):
-            if X is not None and not ContinuousModel._values_are_boolean(X):
-                raise NotImplementedError("GreConD+ takes Boolean (0/1) matrices")
-        bits = BitMatrix(self._X_input, self.device)
-        if bits.max_u8 > 1:
-            raise NotImplementedError("GreConD+ takes Boolean (0/1) matrices")
-        extra = {name: BitMatrix(X, self.device) for name, X in (("val", self.X_val), ("test", self.X_test)) if X is not None}
-        return ExpansionEngine(bits, extra)
+        return ExpansionEngine
 
     # the factors live as packed words (f x W, f x nvw) while the fit runs; U, V, U_exp, V_exp are made from them when it ends
     def truncate_factors(self, k):
         self._Ub, self._Vb = self._Ub[:k], self._Vb[:k]
 
     def _fit(self):
-        from ..grecond import unpack_bits
+        from ..bitset import unpack_bits
         eng = self._engine
         W, nvw = eng.W, eng.nvw
         w_fp = float(self.w_fp)
@@ -128,10 +121,9 @@ class GreConDPlus(GreConD):
             self.n_pruned.append(tuple(eng.pruned))
             self._Ub, self._Vb = Ub, Vb
             eng.rebuild(Ub, Vb)
-            self._counts, self.X_pd = {}, None
+            self._invalidate()
             self.evaluate(df_name='updates', head_info={'k': k, 'score': score, 'shape': [n_u, n_v]})
-            tp, fp, fn, tn = self._counts_of("train")
-            error = 1 - np.float64(tp + tn) / (self.m * self.n)
+            error = self._train_error()
             print("[I] k: {}, score: {}, error: {:.3f}, shape: [{}, {}]".format(k, score, error, n_u, n_v))
             is_factorizing = self.early_stop(error=error, n_factor=k + 1, k=k)
             k = Ub.shape[0]
@@ -139,7 +131,7 @@ class GreConDPlus(GreConD):
 
     def _export(self, Ue, Ve):
         """U, V, U_exp, V_exp as the reference leaves them: lil, float, one column per factor."""
-        from ..grecond import unpack_bits
+        from ..bitset import unpack_bits
 
         def lil(B, length):
             B = np.zeros((0, 1), dtype=np.uint32) if B is None else B

@@ -35,43 +35,23 @@ from __future__ import annotations
 
 import numpy as np
 
-from .BaseModel import BaseModel
-from .ContinuousModel import ContinuousModel
-from .GreConD import GreConD
+from .BooleanModel import BooleanModel
 
 
-class MEBF(BaseModel):
-    device = "cuda:0"
+class MEBF(BooleanModel):
+    title = "MEBF"
 
     def __init__(self, k=None, tol=0, t=None, w_fp=1, w_fn=1):
         self.check_params(k=k, tol=tol, t=t, w_fp=w_fp, w_fn=w_fn)
 
     def fit(self, X_train, X_val=None, X_test=None, **kwargs):
-        if kwargs.get("task", getattr(self, "task", None)) == "prediction":
-            raise NotImplementedError("MEBF scores whole matrices (task='reconstruction'): the scorer of stored entries takes factor "
-                                      "panels of at most 128 columns, not the prediction bits this model keeps")
         if self.t is None:
             raise TypeError("unsupported operand type(s) for *: 'NoneType' and 'float' (MEBF needs the threshold t)")
         super().fit(X_train, X_val, X_test, **kwargs)
-        self._engine = self._make_engine()
-        self._counts = {}
-        self.X_pd = None   # built from the device bits on first access
-        self._fit()
-        self.finish(show_logs=self.show_logs, save_model=self.save_model, show_result=self.show_result)
 
-    _init_factors = GreConD._init_factors
-
-    def _make_engine(self):
-        from ..engine import BitMatrix
+    def _engine_class(self):
         from ..mebf import MedianEngine
-        for X in (self._X_input, self.X_val, self.X_test):
-            if X is not None and not ContinuousModel._values_are_boolean(X):
-                raise NotImplementedError("MEBF takes Boolean (0/1) matrices")
-        bits = BitMatrix(self._X_input, self.device)
-        if bits.max_u8 > 1:
-            raise NotImplementedError("MEBF takes Boolean (0/1) matrices")
-        extra = {name: BitMatrix(X, self.device) for name, X in (("val", self.X_val), ("test", self.X_test)) if X is not None}
-        return MedianEngine(bits, extra)
+        return MedianEngine
 
     # ---- the reference's fp64 expressions on the device's integers --------------------------------------------------------
     def _weighted(self, fp, fn):
@@ -92,7 +72,7 @@ class MEBF(BaseModel):
         self._cut = True
 
     def _kept_factors(self):
-        from ..grecond import pack_bits
+        from ..bitset import pack_bits
         eng, out = self._engine, []
         U, V = np.asarray(self.U.todense()) != 0, np.asarray(self.V.todense()) != 0
         for f in range(U.shape[1]):
@@ -101,7 +81,7 @@ class MEBF(BaseModel):
         return out
 
     def _fit(self):
-        from ..grecond import unpack_bits
+        from ..bitset import unpack_bits
         eng = self._engine
         self.cost = np.float64(eng.sum_x)
         k = 0
@@ -125,10 +105,9 @@ class MEBF(BaseModel):
             self.set_factors(k, u=u.astype(np.float64)[:, None], v=v.astype(np.float64)[:, None])
             self.cost = self.cost + self.d_cost
             eng.apply(c["u"], c["v"], c)
-            self._counts, self.X_pd = {}, None
+            self._invalidate()
             n_u, n_v = int(u.sum()), int(v.sum())
-            tp, fp, fn, tn = self._counts_of("train")
-            error = 1 - np.float64(tp + tn) / (self.m * self.n)
+            error = self._train_error()
             self.print_msg("k: {}, pattern: {}, d_cost: {}, cost: {}, rs: {}, err: {}".format(k, [n_u, n_v], self.d_cost, self.cost,
                                                                                            eng.residual_sum(), error))
             self.evaluate(df_name='updates', head_info={'cost': self.cost, 'shape': [n_u, n_v], 'rs': eng.residual_sum()})
@@ -140,21 +119,3 @@ class MEBF(BaseModel):
             if eng.residual_sum() == 0:
                 break
             k += 1
-
-    # ---- scores --------------------------------------------------------------------------------------------------
-    def _counts_of(self, name):
-        if name not in self._counts:
-            self._counts[name] = self._engine.counts(name)
-        return self._counts[name]
-
-    def _score(self, name, metrics):
-        """Data set `name` against X_pd, from the integer counts of the prediction bits on the device."""
-        if name != "train" and getattr(self, "X_" + name) is None:
-            raise ValueError(f"no {name} data was given to fit()")
-        if any(mt in ("RMSE", "MAE") for mt in metrics):
-            raise NotImplementedError("MEBF scores the Boolean metrics only")
-        return ContinuousModel._metric_values(metrics, None, self._counts_of(name))
-
-    def _make_X_pd(self):
-        """The prediction as the device holds it (after a tolerance stop: with the factor that U, V lost), as csr."""
-        return self._engine.prediction()

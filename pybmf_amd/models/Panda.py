@@ -36,9 +36,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .BaseModel import BaseModel
-from .ContinuousModel import ContinuousModel
-from .GreConD import GreConD
+from .BooleanModel import BooleanModel
 
 
 def order_of(scores):
@@ -46,8 +44,8 @@ def order_of(scores):
     return np.flip(np.argsort(np.asarray(scores), kind="stable"))
 
 
-class Panda(BaseModel):
-    device = "cuda:0"
+class Panda(BooleanModel):
+    title = "Panda"
 
     def __init__(self, k=None, tol=0, w_model=1, w_fp=1, w_fn=1, init_method='correlation', exact_decomp=False):
         self.check_params(k=k, tol=tol, w_model=w_model, w_fp=w_fp, w_fn=w_fn, init_method=init_method, exact_decomp=exact_decomp)
@@ -62,29 +60,11 @@ class Panda(BaseModel):
 
     def fit(self, X_train, X_val=None, X_test=None, **kwargs):
         self._block = kwargs.pop("block", None)
-        if kwargs.get("task", getattr(self, "task", None)) == "prediction":
-            raise NotImplementedError("Panda scores whole matrices (task='reconstruction'): the scorer of stored entries takes factor "
-                                      "panels of at most 128 columns, not the prediction bits this model keeps")
         super().fit(X_train, X_val, X_test, **kwargs)
-        self._engine = self._make_engine()
-        self._counts = {}
-        self.X_pd = None   # built from the device bits on first access
-        self._fit()
-        self.finish(show_logs=self.show_logs, save_model=self.save_model, show_result=self.show_result)
 
-    _init_factors = GreConD._init_factors
-
-    def _make_engine(self):
-        from ..engine import BitMatrix
+    def _engine_class(self):
         from ..panda import PatternEngine
-        for X in (self._X_input, self.X_val, self.X_test):
-            if X is not None and not ContinuousModel._values_are_boolean(X):
-                raise NotImplementedError("Panda takes Boolean (0/1) matrices")
-        bits = BitMatrix(self._X_input, self.device)
-        if bits.max_u8 > 1:
-            raise NotImplementedError("Panda takes Boolean (0/1) matrices")
-        extra = {name: BitMatrix(X, self.device) for name, X in (("val", self.X_val), ("test", self.X_test)) if X is not None}
-        return PatternEngine(bits, extra)
+        return PatternEngine
 
     # ---- the reference's fp64 expressions on the device's integers --------------------------------------------------------
     def _core_d_cost(self, w0, h0, h1):
@@ -168,7 +148,7 @@ class Panda(BaseModel):
         self.cost_now = cost
 
     def _fit(self):
-        from ..grecond import unpack_bits
+        from ..bitset import unpack_bits
         eng = self._engine
         cost_old = self.w_fn * np.float64(eng.sum_x)
         k = 0
@@ -195,28 +175,9 @@ class Panda(BaseModel):
             u_bits, v_bits = eng.apply_core()
             u, v = unpack_bits(u_bits, self.m), unpack_bits(v_bits, self.n)
             self.set_factors(k, u=u.astype(np.float64)[:, None], v=v.astype(np.float64)[:, None])
-            self._counts, self.X_pd = {}, None
+            self._invalidate()
             self.evaluate(df_name='updates', head_info={'cost': self.cost_now, 'shape': [int(n_t), int(n_i)]})
-            tp, fp, fn, tn = self._counts_of("train")
-            error = 1 - np.float64(tp + tn) / (self.m * self.n)
+            error = self._train_error()
             is_improving = self.early_stop(error=error, n_factor=self.n_factors, k=k)
             k += 1
             self.n_factors += 1
-
-    # ---- scores --------------------------------------------------------------------------------------------------
-    def _counts_of(self, name):
-        if name not in self._counts:
-            self._counts[name] = self._engine.counts(name)
-        return self._counts[name]
-
-    def _score(self, name, metrics):
-        """Data set `name` against X_pd, from the integer counts of the prediction bits on the device."""
-        if name != "train" and getattr(self, "X_" + name) is None:
-            raise ValueError(f"no {name} data was given to fit()")
-        if any(mt in ("RMSE", "MAE") for mt in metrics):
-            raise NotImplementedError("Panda scores the Boolean metrics only")
-        return ContinuousModel._metric_values(metrics, None, self._counts_of(name))
-
-    def _make_X_pd(self):
-        """The prediction as the device holds it (after a tolerance stop: with the factor that U, V lost), as csr."""
-        return self._engine.prediction()

@@ -7,6 +7,7 @@ from .BinaryMFThreshold import BinaryMFThreshold
 from .ELBMF import ELBMF
 from .PRIMP import PRIMP
 from .FastStep import FastStep
+from .BooleanModel import BooleanModel
 from .GreConD import GreConD
 from .GreConDPlus import GreConDPlus
 from .Asso import Asso
@@ -15,4 +16,4 @@ from .AssoOpt import AssoOpt
 from .MEBF import MEBF
 from .Panda import Panda
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda"]

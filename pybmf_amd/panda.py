@@ -22,40 +22,29 @@ copied once per sweep (correlation: once per round, with the scores the host sor
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from ._lib import check, lib, ptr
+from .bitset import BitSetEngine, pack_bits, unpack_bits
 from .engine import BitMatrix
-from .grecond import pack_bits, unpack_bits
 
 REC_CORE, REC_EXT, OUT_ROWS, T_AT = 0, 16, 32, 40      # offsets into the state, in 32-bit words
 
 
-class PatternEngine:
+class PatternEngine(BitSetEngine):
+    title = "Panda"
+
     def __init__(self, bits: BitMatrix, extra: dict = None):
-        """bits: the training matrix.  extra: {name: BitMatrix} of further ground truths of the same shape (val / test)."""
-        self.bits, self.m, self.n = bits, bits.m, bits.n
-        self.device = dev = bits.device
+        super().__init__(bits, extra)
+        dev = self.device
         self.W, self.nvw = bits.ldxt, bits.ldx
-        self.sum_x = int(bits.sum_local)
-        self.truth = {"train": bits}
-        for name, B in (extra or {}).items():
-            if (B.m, B.n, B.device) != (bits.m, bits.n, bits.device):
-                raise ValueError(f"the {name} matrix must have the shape and the device of X")
-            self.truth[name] = B
         self.x = [bits.bits_t, bits.bits]
         self.N, self.ld = [self.n, self.m], [self.W, self.nvw]
         W, nvw, n = self.W, self.nvw, self.n
         with torch.cuda.device(dev):
-            need = 4 * (bits.m_pad * bits.n_pad // 8)
-            free_b, _ = torch.cuda.mem_get_info(dev)
-            if need > free_b:
-                raise NotImplementedError(f"Panda on {self.m} x {self.n}: the bits of the residual and of the cover in both orientations take "
-                                          f"{need} more bytes ({need / 2 ** 30:.2f} GiB), {free_b} bytes of device memory are free; "
-                                          "row sharding is not built")
+            self._require_free(4 * (bits.m_pad * bits.n_pad // 8), "the bits of the residual and of the cover in both orientations take",
+                               "; row sharding is not built")
             self.rs = [bits.bits_t.clone(), bits.bits.clone()]
             self.pd = [torch.zeros_like(bits.bits_t), torch.zeros_like(bits.bits)]
             self._count = [torch.zeros(self.N[o], dtype=torch.int32, device=dev) for o in (0, 1)]      # |rs_j| per bit row
@@ -70,10 +59,6 @@ class PatternEngine:
             self._state_host = torch.zeros(T_AT + W + nvw, dtype=torch.int32).pin_memory()
             self._a_host = torch.zeros(n, dtype=torch.int32).pin_memory()
             self._out = torch.zeros(4, dtype=torch.int64, device=dev)
-            self._conf_work = torch.zeros(2 * n, dtype=torch.int32, device=dev)
-            self._conf = torch.zeros(2, dtype=torch.int64, device=dev)
-            self._stream_obj = torch.cuda.current_stream()
-        self._stream = C.c_void_p(self._stream_obj.cuda_stream)
         self._p_core, self._p_ext, self._p_out = self._p(self._state, REC_CORE), self._p(self._state, REC_EXT), self._p(self._state, OUT_ROWS)
         self._p_T, self._p_I = self._p(self._state, T_AT), self._p(self._state, T_AT + W)
         self._host = self._state_host.numpy()
@@ -82,13 +67,6 @@ class PatternEngine:
         with torch.cuda.device(dev), self._on_stream():
             for o in (0, 1):
                 check(lib.bmf_mebf_scores(ptr(self.rs[o]), self.N[o], self.ld[o], ptr(self._count[o]), ptr(self._out), self._stream), "bmf_mebf_scores")
-
-    def _on_stream(self):
-        return torch.cuda.stream(self._stream_obj)
-
-    @staticmethod
-    def _p(tensor, word=0):
-        return C.c_void_p(tensor.data_ptr() + 4 * word)
 
     def _read(self, words, *more):
         """The first `words` words of the state (and further device -> pinned copies) in one wait."""
@@ -200,33 +178,16 @@ class PatternEngine:
         return self._pdsum - tp, self._rsum
 
     def counts(self, name="train"):
-        """(TP, FP, FN, TN) of the cover against data set `name`."""
-        if name == "train":
-            tp = self.sum_x - self._rsum
-            fp, fn = self._pdsum - tp, self._rsum
-        else:
-            G = self.truth[name]
-            with torch.cuda.device(self.device), self._on_stream():
-                check(lib.bmf_bits_confusion(ptr(self.pd[0]), ptr(G.bits_t), self.n, self.W, ptr(self._conf_work), ptr(self._conf), self._stream),
-                      "bmf_bits_confusion")
-                tp, n_pd = (int(x) for x in self._conf.cpu().numpy())
+        """(TP, FP, FN, TN) of the cover against data set `name`; the training set's without a device read."""
+        if name != "train":
             self.reads += 1
-            fp, fn = n_pd - tp, int(G.sum_local) - tp
+            return super().counts(name)
+        fp, fn = self.error_counts()
+        tp = self.sum_x - fn
         return tp, fp, fn, self.m * self.n - tp - fp - fn
 
-    def factor_arrays(self):
-        """(U, V) of the applied factors as uint8 arrays of shape (m, f) and (n, f)."""
-        fs = self._factors
-        U, V = np.zeros((self.m, len(fs)), dtype=np.uint8), np.zeros((self.n, len(fs)), dtype=np.uint8)
-        for i, (u, v) in enumerate(fs):
-            U[:, i], V[:, i] = unpack_bits(u, self.m), unpack_bits(v, self.n)
-        return U, V
-
-    def prediction(self):
-        """X_pd as a scipy csr matrix, from the device bits."""
-        from scipy.sparse import csr_matrix
-        b = self.pd[1][: self.m].cpu().numpy().view(np.uint8)
-        return csr_matrix(np.unpackbits(b, axis=1, bitorder="little")[:, : self.n].astype(int))
+    def _pd_bits(self, for_counts):
+        return (self.pd[0], True) if for_counts else (self.pd[1], False)
 
     def bit_matrices(self):
         """(rs_t, pd_t, rs, pd) as host uint32 arrays (tests)."""

@@ -17,8 +17,9 @@ import numpy as np
 import torch
 from scipy.sparse import csr_matrix
 
+from pybmf_amd.bitset import unpack_bits
 from pybmf_amd.engine import BitMatrix
-from pybmf_amd.grecond import ConceptEngine, unpack_bits
+from pybmf_amd.grecond import ConceptEngine
 from pybmf_amd.models import GreConD
 
 QUIET = dict(task="reconstruction", show_logs=False, show_result=False, save_model=False)

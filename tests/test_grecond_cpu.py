@@ -282,7 +282,7 @@ def test_refusals():
 
 
 def test_pack_helpers_agree_with_the_engine_module():
-    from pybmf_amd.grecond import pack_bits, unpack_bits
+    from pybmf_amd.bitset import pack_bits, unpack_bits
     rng = np.random.RandomState(5)
     for length in (1, 31, 32, 33, 700):
         f = rng.rand(length) < 0.4
