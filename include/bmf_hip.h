@@ -142,6 +142,22 @@ int bmf_xf_bits_i8_occupancy(int limbs); /* workgroups per CU the runtime grants
 int bmf_xf_bits_i8_variant(int v);
 int bmf_xf_bits_i8(const uint32_t* Abits, int64_t rows_pad, int64_t ldw, int64_t red_words, const int8_t* panel, int64_t ldp,
                    int limbs, const float* colscale, int kp, float* out, int64_t slab_stride, int splits, int a_tiled, void* stream);
+/* The launch form of the iteration driver: columns [col0, col0 + ncols) of the kp-wide factor (ncols 32 or 64, col0 % 32 == 0; the
+ * other columns of `out` are not touched), under the plan of an ncols-wide launch (splits >= its slots: bmf_xf_bits_i8_plan), and a
+ * device flag `stop` (NULL: none): when *stop != 0 the launch writes nothing.  bmf_xf_bits_i8 is (col0, ncols, stop) = (0, kp, NULL). */
+int bmf_xf_bits_i8_cols(const uint32_t* Abits, int64_t rows_pad, int64_t ldw, int64_t red_words, const int8_t* panel, int64_t ldp,
+                        int limbs, const float* colscale, int kp, int col0, int ncols, float* out, int64_t slab_stride, int splits,
+                        int a_tiled, const int32_t* stop, void* stream);
+/* The stream-K plan such a launch runs under (host arithmetic; all outputs are HOST pointers).  The (row tile, stage) units -- stage = 128
+ * reduction indices, unit u = tile * (red_words / 4) + stage, `total` of them -- are cut into n_slices logical slices: the first n_big are
+ * u_big units long, the rest u_small, the last one clipped by `total`.  Slice s of the launch writes, for every row tile it meets, its
+ * partial sum into slab slot s - (the slice that holds the tile's first unit); the slice that holds a tile's last unit zero-fills the
+ * slots behind its own up to `splits`.  plan (8 values): n_slices, grid (workgroups), n_big, u_big, u_small, slots, column halves
+ * (workgroups per slice), rows per tile -- the last two of the kernel variant in force (bmf_xf_bits_i8_variant).  perm (512 values, may be
+ * NULL): perm[b] = the logical slice of block slice b (0xFFFF: none); workgroup w runs block slice (w / 8 / halves) * 8 + w % 8.
+ * cus > 0: the plan for a device with that many compute units, without touching a device; cus == 0: the current device's count.
+ * Arguments are checked as by the launch; a refused call writes nothing. */
+int bmf_xf_bits_i8_plan(int64_t rows_pad, int64_t red_words, int ncols, int kp, int cus, int32_t* plan, int64_t* total, uint16_t* perm);
 /* The bit matrix re-laid for that kernel (a_tiled = 1): the 256 rows x 16 words one workgroup consumes per group of four stages
  * become one contiguous 16-KiB block, blocks in (row tile, group) order:
  *   tiled[((tile * (red_words / 16) + grp) * 256 + row) * 16 + w] = bits[(tile * 256 + row) * ldw + 16 * grp + w].
@@ -189,6 +205,17 @@ int bmf_s24_overflow(const int64_t* ovf_ptr, const int32_t* ovf_idx, const int32
  * scale (out): 2 * kp floats. */
 int bmf_make_panel_i8(const double* F64, const float* F, int64_t rows_pad, int64_t ldf, int kp, int limbs, int8_t* panel,
                       int64_t ldp, float* ws, float* scale, void* stream);
+/* The conditional rebuild of the iteration driver, after bmf_gram_partial_i8(fused = 1): scale = the exact scales ([kp], its block
+ * [2 kp, 3 kp)), flags = its block [3 kp, 4 kp).  No flagged column: the planes are left alone.  1 to 8: the digits of those columns only
+ * are rewritten at the exact scale, everything else (colscale_out too) is left alone.  More: all planes are rebuilt at the exact
+ * scales and colscale_out[c] = (limbs == 2 ? 256 : 1) / scale[c].
+ * rslabs != NULL: rn / 16 extra workgroups (rn % 16 == 0) sum rcount slabs of rn floats, rout[i] = sum_b rslabs[b * rn + i], in fp64:
+ * 16 groups of ceil(rcount / 16) consecutive slabs summed in slab order, the 16 group sums added in group order -- rout32 / rout64
+ * (either may be NULL) then hold, bit for bit, what bmf_reduce_slabs gives for the same slabs (n < 65536).
+ * *stop != 0 (stop may be NULL): planes and colscale_out are left alone, rout32 too, and rout64 is ZEROED. */
+int bmf_make_panel_i8_cond(const double* F64, int64_t rows_pad, int64_t ldf, int kp, int limbs, int8_t* panel, int64_t ldp,
+                           const float* scale, const float* flags, float* colscale_out, const float* rslabs, int rcount, int rn,
+                           float* rout32, double* rout64, const int32_t* stop, void* stream);
 
 /* Same contraction for a real-valued fp32 A (WNMF on non-Boolean data): exact-fp32 MFMA
  * (v_mfma_f32_32x32x2_f32).  A: rows_pad x lda floats, reduction length red (multiple of 8, zero padded),
@@ -237,6 +264,18 @@ int bmf_frag_rows_bf16(const float* F, int64_t rows_pad, int kp, uint32_t* frag,
  * Together with bmf_reduce_slabs this is U^T U / V^T V, i.e. the re-associated denominators
  * (U V^T)^T U = V (U^T U)  models/BinaryMFPenalty.py:142,157; WNMF.py:99,106. */
 int bmf_gram_partial(const float* F, int64_t rows_pad, int64_t ldf, int kp, float* slabs, int blocks, void* stream);
+/* The Gram launch of the iteration driver: the same slabs, and kp / 4 extra workgroups that take the column maxima of F from
+ * blockmax ([rows_pad / 128][kp], max|F| per 128-row block; rows_pad % 128 == 0) and write the column scales of the int8 digit planes:
+ *   fused = 0: scale (2 * kp floats) as bmf_make_panel_i8 writes them.
+ *   fused = 1: the planes exist already, built with the predicted scale in scale[0, kp).  scale is 4 * kp floats:
+ *     [0, kp) in: the scale the planes were built with; out: the exact scale of the new maxima (the next prediction);
+ *     [kp, 2 kp) out: the GEMM's colscale for the planes as they will stand: (limbs == 2 ? 256 : 1) / (the scale kept, else the exact one);
+ *     [2 kp, 3 kp) out: the exact scale;  [3 kp, 4 kp) out: 1.0 where the prediction was off (bmf_make_panel_i8_cond rebuilds those
+ *     columns), else 0.0.  A prediction is kept while max * scale lies in [2^21, 8355711], or the column is all zero; a scale that is
+ *     zero, negative, infinite or NaN is never kept.
+ * *stop != 0 (stop may be NULL): the scale workgroups write nothing; the Gram slabs are written all the same. */
+int bmf_gram_partial_i8(const float* F, int64_t rows_pad, int64_t ldf, int kp, float* slabs, int blocks, const float* blockmax, int limbs,
+                        float* scale, int fused, const int32_t* stop, void* stream);
 
 /* out32[i] / out64[i] = sum_b slabs[b*stride + i] (fp64 accumulation, fixed order); either output may be NULL. */
 int bmf_reduce_slabs(const float* slabs, int64_t stride, int count, int64_t n, float* out32, double* out64,

@@ -160,6 +160,8 @@ SIGNATURES = {
     "bmf_xf_bits_i8_occupancy": (C.c_int, [C.c_int]),
     "bmf_xf_bits_i8_variant": (C.c_int, [C.c_int]),
     "bmf_xf_bits_i8": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, C.c_int, _vp, C.c_int, _vp, _i64, C.c_int, C.c_int, _vp]),
+    "bmf_xf_bits_i8_cols": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
+    "bmf_xf_bits_i8_plan": (C.c_int, [_i64, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(C.c_uint16)]),
     "bmf_tile_bits": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "bmf_s24_bytes": (_i64, [_i64, _i64]),
     "bmf_s24_count": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
@@ -172,6 +174,8 @@ SIGNATURES = {
     "bmf_make_panel_i8": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp]),
     "bmf_xf_f32": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, C.c_int, _vp, _i64, C.c_int, _vp]),
     "bmf_gram_partial": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp]),
+    "bmf_gram_partial_i8": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "bmf_make_panel_i8_cond": (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "bmf_reduce_slabs": (C.c_int, [_vp, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "bmf_mu_epilogue": (C.c_int, [C.POINTER(EpilogueArgs), _vp]),
     "bmf_masked_pass": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),

@@ -442,6 +442,14 @@ extern "C" int bmf_gram_partial(const float* F, int64_t rows_pad, int64_t ldf, i
     return bmf_gram_partial_launch(F, rows_pad, ldf, kp, slabs, blocks, nullptr, 0, nullptr, nullptr, (hipStream_t)stream, 0);
 }
 
+// the Gram launch of the iteration driver: kp / 4 extra blocks derive (fused = 0) or check (fused = 1) the int8 column scales
+extern "C" int bmf_gram_partial_i8(const float* F, int64_t rows_pad, int64_t ldf, int kp, float* slabs, int blocks, const float* blockmax,
+                                   int limbs, float* scale, int fused, const int32_t* stop, void* stream) {
+    BMF_REQUIRE(blockmax && scale, "bmf_gram_partial_i8: null pointer");
+    BMF_REQUIRE(fused == 0 || fused == 1, "bmf_gram_partial_i8: fused=%d must be 0 or 1", fused);
+    return bmf_gram_partial_launch(F, rows_pad, ldf, kp, slabs, blocks, blockmax, limbs, scale, stop, (hipStream_t)stream, fused);
+}
+
 
 // ---- sum(W o (A - B)^2) for dense fp64 arrays: rec_error(X_gt, X_pd, W) with an explicit prediction (the caller applies the 0.5) ---
 namespace {

@@ -794,6 +794,37 @@ extern "C" int bmf_xf_bits_i8_slots(int64_t rows_pad, int64_t red_words, int kp)
     return make_plan_i8(rows_pad, (int)(red_words / 4), kp, bmf_i8_use_wide(kp, kp)).slots;
 }
 
+// The stream-K plan of a launch, for tests and for callers that want to know where a slab comes from.  Host arithmetic only: with
+// cus > 0 the plan is cut for that many compute units (no device, no cache); cus == 0 takes the current device's count, as a launch does.
+extern "C" int bmf_xf_bits_i8_plan(int64_t rows_pad, int64_t red_words, int ncols, int kp, int cus, int32_t* plan, int64_t* total,
+                                   uint16_t* perm) {
+    BMF_REQUIRE(plan && total, "bmf_xf_bits_i8_plan: null pointer");
+    BMF_REQUIRE(rows_pad > 0 && rows_pad % BMF_ROW_PAD == 0, "bmf_xf_bits_i8_plan: rows_pad=%lld must be a positive multiple of %d",
+                (long long)rows_pad, BMF_ROW_PAD);
+    BMF_REQUIRE(red_words > 0 && red_words % 16 == 0, "bmf_xf_bits_i8_plan: red_words=%lld must be a positive multiple of 16 (reduction padded to 512)", (long long)red_words);
+    BMF_REQUIRE(red_words * 32 < (1 << 24), "bmf_xf_bits_i8_plan: reduction length %lld would overflow the int32 accumulators",
+                (long long)red_words * 32);
+    BMF_REQUIRE(rows_pad / 256 <= INT32_MAX / (red_words / 4), "bmf_xf_bits_i8_plan: too many (row tile, stage) units");
+    BMF_REQUIRE(kp == 32 || kp == 64, "bmf_xf_bits_i8_plan: kp=%d must be 32 or 64", kp);
+    BMF_REQUIRE((ncols == 32 || ncols == 64) && ncols <= kp, "bmf_xf_bits_i8_plan: ncols=%d must be 32 or 64 and at most kp=%d", ncols, kp);
+    BMF_REQUIRE(cus == 0 || (cus >= 2 && cus <= 65536), "bmf_xf_bits_i8_plan: cus=%d must be 0 (the current device) or 2..65536", cus);
+    const int stages = (int)(red_words / 4);
+    const int wide = bmf_i8_use_wide(ncols, kp);
+    const PlanI8 pl = cus > 0 ? build_plan_i8(rows_pad, stages, ncols, cus, wide) : make_plan_i8(rows_pad, stages, ncols, wide);
+    plan[0] = pl.n_slices;
+    plan[1] = pl.grid;
+    plan[2] = pl.n_big;
+    plan[3] = pl.u_big;
+    plan[4] = pl.u_small;
+    plan[5] = pl.slots;
+    plan[6] = (wide && wide != 4) ? 1 : ncols / 32;   // column halves (workgroups per slice)
+    plan[7] = (wide == 3 || wide == 4) ? 512 : 256;   // rows per tile
+    *total = pl.total;
+    if (perm)
+        for (int b = 0; b < 512; ++b) perm[b] = pl.perm.p[b];
+    return BMF_OK;
+}
+
 int bmf_blockmax_launch(const float* F, int64_t rows_pad, int64_t ldf, int kp, float* ws, const int32_t* stop, hipStream_t s);
 
 // col0, ncols: the column range of the kp-wide factor this launch computes (the whole factor: 0, kp); the other columns of `out`
@@ -829,6 +860,14 @@ extern "C" int bmf_xf_bits_i8(const uint32_t* Abits, int64_t rows_pad, int64_t l
                               void* stream) {
     return bmf_xf_bits_i8_launch(Abits, rows_pad, ldw, red_words, panel, ldp, limbs, colscale, kp, 0, kp, out, slab_stride, splits, a_tiled,
                                  nullptr, (hipStream_t)stream);
+}
+
+// the launch form of the iteration driver: a 32- or 64-column block of the factor, and the device stop flag
+extern "C" int bmf_xf_bits_i8_cols(const uint32_t* Abits, int64_t rows_pad, int64_t ldw, int64_t red_words, const int8_t* panel, int64_t ldp,
+                                   int limbs, const float* colscale, int kp, int col0, int ncols, float* out, int64_t slab_stride, int splits,
+                                   int a_tiled, const int32_t* stop, void* stream) {
+    return bmf_xf_bits_i8_launch(Abits, rows_pad, ldw, red_words, panel, ldp, limbs, colscale, kp, col0, ncols, out, slab_stride, splits, a_tiled,
+                                 stop, (hipStream_t)stream);
 }
 
 namespace {
@@ -890,4 +929,16 @@ int bmf_panel_i8_launch(const double* F64, const float* F, int64_t rows_pad, int
 extern "C" int bmf_make_panel_i8(const double* F64, const float* F, int64_t rows_pad, int64_t ldf, int kp, int limbs, int8_t* panel,
                                  int64_t ldp, float* ws, float* scale, void* stream) {
     return bmf_panel_i8_launch(F64, F, rows_pad, ldf, kp, limbs, panel, ldp, ws, scale, false, nullptr, (hipStream_t)stream, false, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr);
+}
+
+// the conditional rebuild as the iteration driver launches it: column maxima and scales exist already (bmf_gram_partial_i8, fused),
+// `flags` says which columns to rebuild, and the slab reduction of the Gram launch may ride along (rslabs != NULL)
+extern "C" int bmf_make_panel_i8_cond(const double* F64, int64_t rows_pad, int64_t ldf, int kp, int limbs, int8_t* panel, int64_t ldp,
+                                      const float* scale, const float* flags, float* colscale_out, const float* rslabs, int rcount, int rn,
+                                      float* rout32, double* rout64, const int32_t* stop, void* stream) {
+    BMF_REQUIRE(F64 && panel && scale && flags && colscale_out, "bmf_make_panel_i8_cond: null pointer");
+    // (ws: the column maxima are not looked at in this form; the launcher only asks for a non-null pointer)
+    float* sc = const_cast<float*>(scale);
+    return bmf_panel_i8_launch(F64, nullptr, rows_pad, ldf, kp, limbs, panel, ldp, sc, sc, true, stop, (hipStream_t)stream, true, flags, colscale_out,
+                               rslabs, rcount, rn, rout32, rout64);
 }

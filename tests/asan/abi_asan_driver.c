@@ -93,6 +93,31 @@ int main(void) {
         if (bmf_residual_plan(128, 32769, &pa, &pb) != 0 || pa != 513 || pb != 2) ++fails;
         if (bmf_residual_tiled_plan(64, 64 * 17, &pa, &pb) != 0 || pa != 2 || pb != 9) ++fails;
     }
+    {   /* the int8 GEMM's plan query (host arithmetic for cus > 0) and the launch forms of the iteration driver */
+        int32_t plan[8];
+        int64_t total = -7;
+        uint16_t perm[512];
+        for (int i = 0; i < 8; ++i) plan[i] = -7;
+        EXPECT_REFUSED(bmf_xf_bits_i8_plan(512, 16, 32, 32, 256, NULL, &total, perm));
+        EXPECT_REFUSED(bmf_xf_bits_i8_plan(500, 16, 32, 32, 256, plan, &total, perm));
+        EXPECT_REFUSED(bmf_xf_bits_i8_plan(512, 12, 32, 32, 256, plan, &total, perm));
+        EXPECT_REFUSED(bmf_xf_bits_i8_plan(512, 16, 64, 32, 256, plan, &total, perm));
+        EXPECT_REFUSED(bmf_xf_bits_i8_plan(512, 16, 32, 32, -1, plan, &total, perm));
+        if (plan[0] != -7 || plan[7] != -7 || total != -7) ++fails;
+        if (bmf_xf_bits_i8_plan(100352, 640, 64, 64, 256, plan, &total, perm) != 0 || plan[0] != 255 || plan[2] != 128 || plan[3] != 324 ||
+            plan[4] != 168 || plan[5] != 2 || plan[6] != 2 || plan[7] != 256 || total != 392 * 160)
+            ++fails;
+        if (bmf_xf_bits_i8_plan(512, 16, 32, 32, 256, plan, &total, NULL) != 0 || plan[0] != 2 || plan[3] != 4 || total != 8) ++fails;
+        EXPECT_REFUSED(bmf_xf_bits_i8_cols(bits, 512, 16, 16, (const int8_t*)junk, 512, 3, f, 64, 16, 32, f, 512 * 64, 1, 0, NULL, NULL));
+        EXPECT_REFUSED(bmf_xf_bits_i8_cols(bits, 512, 16, 16, (const int8_t*)junk, 512, 3, f, 64, 32, 64, f, 512 * 64, 1, 0, NULL, NULL));
+        EXPECT_REFUSED(bmf_xf_bits_i8_cols(bits, 512, 16, 16, (const int8_t*)junk, 512, 3, f, 64, 0, 48, f, 512 * 64, 1, 0, NULL, NULL));
+        EXPECT_REFUSED(bmf_gram_partial_i8(f, 512, 64, 64, f, 4, NULL, 3, f, 1, NULL, NULL));
+        EXPECT_REFUSED(bmf_gram_partial_i8(f, 512, 64, 64, f, 4, f, 4, f, 1, NULL, NULL));
+        EXPECT_REFUSED(bmf_gram_partial_i8(f, 512, 64, 64, f, 4, f, 3, f, 2, NULL, NULL));
+        EXPECT_REFUSED(bmf_make_panel_i8_cond((const double*)junk, 512, 64, 64, 3, (int8_t*)junk, 512, f, NULL, f, NULL, 0, 0, NULL, NULL, NULL, NULL));
+        EXPECT_REFUSED(bmf_make_panel_i8_cond((const double*)junk, 500, 64, 64, 3, (int8_t*)junk, 512, f, f, f, NULL, 0, 0, NULL, NULL, NULL, NULL));
+        EXPECT_REFUSED(bmf_make_panel_i8_cond((const double*)junk, 512, 64, 64, 3, (int8_t*)junk, 512, f, f, f, f, 3, 100, f, NULL, NULL, NULL));
+    }
     EXPECT_REFUSED(bmf_link_pass(NULL, 512, 4, 1, 1, NULL, NULL, 512, 32, 1, 10.0, NULL, NULL, 512 * 32, 1, NULL));
     EXPECT_REFUSED(bmf_link_split(NULL, 512, 32, NULL, NULL));
     EXPECT_REFUSED(bmf_link_pass16(NULL, 512, 4, 1, 1, NULL, NULL, 512, 32, 1, 10.0, NULL, NULL, 512 * 32, 1, NULL));

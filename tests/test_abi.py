@@ -67,7 +67,8 @@ def test_bad_arguments_are_refused_without_a_gpu():
 
 def test_host_only_launch_plan_queries():
     """bmf_residual_plan and bmf_residual_tiled_plan are host arithmetic: bad arguments are refused, and the grids are the ones worked
-    out by hand from the rules in their launchers (csrc/residual.hip, csrc/resid_f32.hip)."""
+    out by hand from the rules in their launchers (csrc/residual.hip, csrc/resid_f32.hip).  bmf_xf_bits_i8_plan with an explicit
+    compute-unit count is host arithmetic as well: its argument checks are here, its plans in tests/test_i8_plan_cpu.py."""
     from pybmf_amd import _lib as L
     lib = L.lib
     a, b = C.c_int(-7), C.c_int(-7)
@@ -108,6 +109,26 @@ def test_host_only_launch_plan_queries():
     assert lib.bmf_mae_plan(256, 64, None, C.byref(b)) == -1 and b"bmf_mae_plan: null pointer" in lib.bmf_last_error()
     for bad in ((0, 64), (255, 64), (256, 0), (256, 65), (-256, 64), (1 << 32, 64)):
         assert lib.bmf_mae_plan(bad[0], bad[1], C.byref(a), C.byref(b)) == -1 and b"bmf_mae_plan" in lib.bmf_last_error(), bad
+    # bmf_xf_bits_i8_plan with an explicit compute-unit count is host arithmetic too: its arguments are checked as the launch checks them
+    f, total, perm = (C.c_int32 * 8)(*([-7] * 8)), C.c_int64(-7), (C.c_uint16 * 512)(*([7] * 512))
+    good = dict(rows_pad=1024, red_words=32, ncols=32, kp=64, cus=256)
+
+    def i8_plan(plan=f, tot=total, pm=perm, **kw):
+        a_ = dict(good, **kw)
+        return lib.bmf_xf_bits_i8_plan(a_["rows_pad"], a_["red_words"], a_["ncols"], a_["kp"], a_["cus"], plan, C.byref(tot) if tot is not None else None, pm)
+
+    assert i8_plan(plan=None) == -1 and b"bmf_xf_bits_i8_plan: null pointer" in lib.bmf_last_error()
+    assert i8_plan(tot=None) == -1 and b"bmf_xf_bits_i8_plan: null pointer" in lib.bmf_last_error()
+    for bad in (dict(rows_pad=0), dict(rows_pad=-512), dict(rows_pad=1000), dict(rows_pad=768), dict(red_words=0), dict(red_words=-16),
+                dict(red_words=24), dict(red_words=1 << 19), dict(ncols=0), dict(ncols=16), dict(ncols=48), dict(ncols=96),
+                dict(ncols=64, kp=32), dict(kp=48), dict(kp=128), dict(cus=-1), dict(cus=1), dict(cus=1 << 20),
+                dict(rows_pad=1 << 40, red_words=(1 << 19) - 16)):
+        assert i8_plan(**bad) == -1 and b"bmf_xf_bits_i8_plan" in lib.bmf_last_error(), bad
+        assert list(f) == [-7] * 8 and total.value == -7 and list(perm) == [7] * 512, bad      # a refused call writes nothing
+    assert i8_plan() == 0 and list(f) == [8, 8, 0, 4, 4, 2, 1, 256] and total.value == 32       # 4 tiles x 8 stages: 8 slices of one group
+    assert sorted(perm) == list(range(8)) + [0xFFFF] * 504
+    f[0] = -7
+    assert i8_plan(pm=None) == 0 and f[0] == 8                                                  # the slice map is optional
     import objective_ref as R
     for m, n in ((1, 1), (130, 70), (128, 65606), (8192, 1083), (100000, 20000), (20, 33000)):
         assert plan(lib.bmf_residual_plan, m, n) == R.residual_plan(m, n)
