@@ -827,6 +827,26 @@ int bmf_panda_rows(const uint32_t* rs, const uint32_t* pd, int32_t m, int64_t ld
                    int64_t n_i, uint32_t* T, int64_t ldt, double w_model, double w_fp, double w_fn, void* work, int64_t* out,
                    void* stream);
 
+/* ---- Hyper: itemset mining and hyperrectangle records on bit sets (csrc/hyper.hip) ------------------------------------------------
+ * PyBMF/models/Hyper.py:44-82, 147-186.  Every array of bit rows has ld = m_pad / 32 words per row (a multiple of 4, 16-byte aligned,
+ * zero padded): x_t and rs_t are X and the residual transposed (bit row j = column j, n rows), a tidset is the AND of x_t[j] over the
+ * columns j of an itemset.  Exact integers, no atomics; the support test and the costs are host fp64 on these integers.
+ *
+ * bmf_hyper_level: for c < count: tid_out[c] = tid_prev[pair[2 c]] & x_t[pair[2 c + 1]], cnt[c] = |tid_out[c]|.  A pair whose parent
+ *   slot is outside [0, n_prev) or whose column is outside [0, n) gives an empty row and the count 0.
+ * bmf_hyper_eval: for i < count and id = ids[i] in [0, n_cand) (another id is skipped), with I = the columns items[id * maxlen ..] up
+ *   to the first -1: T = tid[id] & OR_{j in I} rs_t[j] is written to T_out[id], rec[2 id] = |T|, rec[2 id + 1] = the sum over j in I
+ *   of |tid[id] & rs_t[j]|.  T is the set of rows that hold all of I in X and a residual one on I (find_hyper's queue; its greedy
+ *   test always passes), the sum is X_rs[T, I].sum().
+ * bmf_hyper_copy: dst[dst_id[i]] = src[src_id[i]] for i < count; a pair with an id outside [0, n_src) or [0, n_dst) is skipped.  src
+ *   and dst are different arrays.  With the same list on both sides it commits scratch T rows; it also compacts a mined level. */
+int bmf_hyper_level(const uint32_t* tid_prev, int32_t n_prev, const uint32_t* x_t, int32_t n, int64_t ld, const int32_t* pair,
+                    int32_t count, uint32_t* tid_out, int32_t* cnt, void* stream);
+int bmf_hyper_eval(const uint32_t* tid, const uint32_t* rs_t, int32_t n, int64_t ld, const int32_t* items, int32_t maxlen,
+                   const int32_t* ids, int32_t count, int32_t n_cand, uint32_t* T_out, int32_t* rec, void* stream);
+int bmf_hyper_copy(const uint32_t* src, int32_t n_src, const int32_t* src_id, uint32_t* dst, int32_t n_dst, const int32_t* dst_id,
+                   int64_t ld, int32_t count, void* stream);
+
 /* ---- GreConD+: factor expansion, rebuild and overlap pruning on bit sets (csrc/grecondplus.hip) -----------------------------------
  * PyBMF/models/GreConDPlus.py:131-308.  A bit matrix is `lines` bit rows of ld words, zero padded: row-major (line = row of X, ld = n_pad
  * / 32) or transposed (line = column of X, ld = m_pad / 32).  RS = X & ~PD is the residual, which an expansion holds fixed.  Exact

@@ -262,6 +262,9 @@ SIGNATURES = {
     "bmf_panda_ext_scan": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _i64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "bmf_panda_rows_work": (_i64, [_i32]),
     "bmf_panda_rows": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "bmf_hyper_level": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "bmf_hyper_eval": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "bmf_hyper_copy": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp]),
     "bmf_expand_counts": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
     "bmf_expand_rec_words": (_i64, [_i32, _i32]),
     "bmf_expand_steps": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -15,5 +15,6 @@ from .AssoIter import AssoIter
 from .AssoOpt import AssoOpt
 from .MEBF import MEBF
 from .Panda import Panda
+from .Hyper import Hyper
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper"]
