@@ -420,6 +420,17 @@ int bmf_cover_count(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, int64_
                     const uint32_t* colbits, int64_t ldcb, int kp, unsigned long long* counts, const int32_t* stop,
                     void* stream);
 
+/* The change of those two counts when the k-bit words of some rows change and the bit-columns stay as they are:
+ *   counts[0] += sum_i |B_i & P(rowbits[i])| - |B_i & P(rowbits_prev[i])|,  counts[1] += the same with ~B_i,  P(u) = OR_{l in u} colbits_l,
+ * added as two's complement (the 64-bit counters wrap to the right sum).  Only rows with rowbits[i] != rowbits_prev[i] are read; the
+ * cost is proportional to their number.  `bits`: rows_pad x ld words, plain row-major -- X with U's words and V's bit-columns, or X^T
+ * with V's words and U's bit-columns.  rows_pad % 64 == 0; words % 4 == 0, >= 4.  rowbits_prev is NOT written.  With copy_n > 0 the launch
+ * also copies copy_src[0 .. copy_n) to copy_dst (words it does not read: the other orientation's previous words, see
+ * bmf_penalty_state.ubits_prev).  Nothing moves when *stop != 0. */
+int bmf_cover_delta(const uint32_t* bits, int64_t ld, int64_t words, int64_t rows_pad, const uint64_t* rowbits,
+                    const uint64_t* rowbits_prev, const uint32_t* colbits, int64_t ldcb, int kp, unsigned long long* counts,
+                    const uint64_t* copy_src, uint64_t* copy_dst, int64_t copy_n, const int32_t* stop, void* stream);
+
 /* Per-row confusion counts of two bit matrices of equal shape (ground truth G, prediction P):
  * tp[r] = |G_r and P_r|, fp[r] = |not G_r and P_r|  -- TP / FP with axis=1 of utils/metrics.py:56-68 (pass the transposed
  * bit matrices for axis=0); FN = rowsum(G) - TP, TN follows.  Feeds coverage_score / weighted_error (metrics.py:182-201). */
@@ -498,7 +509,8 @@ typedef struct {
     double* scal;                         /* [8]: [0]=sum(V^2-V)^2 (replicated), [1]=previous reg_error, rest spare */
     uint64_t* ubits; uint32_t* ucolbits; int64_t lduc; /* [m_pad], [kp][m_pad/32] */
     uint64_t* vbits; uint32_t* vcolbits; int64_t ldvc; /* [n_pad], [kp][n_pad/32] */
-    unsigned long long* counts;           /* [4] local TP, FP, spare */
+    unsigned long long* counts;           /* [4] local TP, FP as the launches of one sweep add them (reset by the gather); [2], [3]: the running
+                                             local TP, FP when ubits_prev / vbits_prev are set, spare otherwise */
     double* log;                          /* [log_rows][BMF_LOG_COLS] */
     int32_t log_rows; int32_t _pad3;
     int32_t* stop;                        /* device flag: 0 running, else the iteration that tripped early stop */
@@ -528,6 +540,16 @@ typedef struct {
                                              2 = yes -- the caller's decision, which MUST be the same on every rank (the two forms issue
                                              different collectives: decide from rank-invariant quantities, e.g. the largest shard);
                                              0 = the library decides from THIS state (one rank, or equal shards) */
+    uint64_t* ubits_prev; uint64_t* vbits_prev; /* [m_pad], [n_pad], both NULL or both set.  NULL: the cover count is a full pass over X
+                                             in every sweep.  Set: the PREPARE sweep counts in full, keeps the local TP / FP in counts[2],
+                                             counts[3] and the k-bit words here; every update then adds only the change (bmf_cover_delta:
+                                             the columns whose vbits word changed, on X^T against U's old bit-columns, right after the V
+                                             update; the rows whose ubits word changed, on X against V's new bit-columns, after the U
+                                             update).  INVARIANT: the TP / FP of a log row are valid if every update since the last PREPARE
+                                             sweep ran both passes on this state -- factors replaced from outside (or updates_only, the
+                                             thresholds or the pointers changed) need a new bmf_penalty_prepare[_sharded] to re-base.
+                                             After a raised stop flag nothing runs, the totals stay.  Row-sharded: every rank keeps the
+                                             totals of its own rows; comm[2], comm[3] carry them into the all-reduce as before. */
 } bmf_penalty_state;
 
 /* Build panels, bits, Grams, partial sums and X V, X^T U from the initial U, V (iteration-0 bookkeeping,
@@ -537,7 +559,9 @@ int bmf_penalty_prepare(const bmf_penalty_state* st, void* stream);
 
 /* One multiplicative-update iteration with regulariser `reg`: V epilogue, X V, U epilogue, Grams, cover count,
  * X^T U of the NEW U (the numerator of the next V update, so that one exchange per iteration carries everything --
- * SURVEY section 8e), Grams, cover count.  Leaves local partial results in Nred / comm. */
+ * SURVEY section 8e), Grams, cover count.  Leaves local partial results in Nred / comm.  With st->ubits_prev / vbits_prev set the
+ * cover count is the change over the changed columns (after the V epilogue) and rows (after the U epilogue) added to running totals:
+ * see the invariant at those fields. */
 int bmf_penalty_update(const bmf_penalty_state* st, double reg, void* stream);
 
 /* The same iteration in phases, for the sharded loop: _head = V update, V^T V, X V, U update and the scalar part (U^T U, cover

@@ -133,6 +133,7 @@ class PenaltyState(C.Structure):
         ("panel_kind", _i32), ("updates_only", _i32),
         ("scaleU", _vp), ("scaleV", _vp), ("panel_ws", _vp), ("mae_ws", _vp),
         ("Xtiled", _vp), ("XTtiled", _vp), ("nred_blocks", _i32), ("exchange_overlap", _i32),
+        ("ubits_prev", _vp), ("vbits_prev", _vp),
     ]
 
 
@@ -191,6 +192,7 @@ SIGNATURES = {
     "bmf_mae_sum_tiled": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "bmf_mae_plan": (C.c_int, [_i64, _i64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmf_cover_count": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
+    "bmf_cover_delta": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _i64, _vp, _vp]),
     "bmf_boolean_product_bits": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _i64, _vp, _i64, _vp]),
     "bmf_real_product": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, C.c_int, _vp, _i64, _vp]),
     "bmf_residual_sums": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, C.c_int, _vp, _vp, _vp]),

@@ -29,6 +29,9 @@ int bmf_xf_bits_i8_launch(const uint32_t* Abits, int64_t rows_pad, int64_t ldw, 
 int bmf_cover_launch(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, int64_t words, const uint64_t* rowbits,
                      const uint32_t* colbits, int64_t ldcb, int kp, unsigned long long* counts, const int32_t* stop,
                      hipStream_t s);
+int bmf_cover_delta_launch(const uint32_t* bits, int64_t ld, int64_t words, int64_t rows_pad, const uint64_t* rowbits,
+                           const uint64_t* rowbits_prev, const uint32_t* colbits, int64_t ldcb, int kp, unsigned long long* counts,
+                           const uint64_t* copy_src, uint64_t* copy_dst, int64_t copy_n, const int32_t* stop, hipStream_t s);
 int bmf_residual_launch(const uint32_t* Xbits, int64_t m_pad, int64_t ldx, int m, int n, const float* A, const float* B,
                         const float* dA, const float* dB, int kp, double* sums, const int32_t* stop, hipStream_t s);
 
@@ -105,10 +108,11 @@ extern "C" int bmf_timer_disable(void) {
 namespace {
 
 // local partial sums -> comm block (what gets all-reduced); resets the local integer counters.  Called by all threads of a block
-// of >= 256 threads; `sh`: 768 doubles of LDS.
+// of >= 256 threads; `sh`: 768 doubles of LDS.  delta: counts[0], counts[1] hold what this sweep's launches added -- the full count
+// after a PREPARE sweep (which zeroed the totals), the signed change of an update -- and counts[2], counts[3] the running local TP, FP.
 __device__ __forceinline__ void gather_body(const double* __restrict__ partU, int nbU, const double* __restrict__ partV, int nbV,
                                             unsigned long long* __restrict__ counts, double* __restrict__ comm,
-                                            double* __restrict__ scal, double* sh) {
+                                            double* __restrict__ scal, double* sh, int delta) {
     const int tid = threadIdx.x;
     if (tid < 256) {
         double regU = 0.0, dot = 0.0, regV = 0.0;
@@ -133,8 +137,16 @@ __device__ __forceinline__ void gather_body(const double* __restrict__ partU, in
     if (tid == 0) {
         comm[0] = sh[256];  // sum U o (X V)
         comm[1] = sh[0];    // sum (U^2 - U)^2
-        comm[2] = (double)counts[0];
-        comm[3] = (double)counts[1];
+        if (delta) {
+            for (int c = 0; c < 2; ++c) {
+                const unsigned long long tot = counts[2 + c] + counts[c];   // (two's complement: a negative change wraps to the right total)
+                counts[2 + c] = tot;
+                comm[2 + c] = (double)tot;
+            }
+        } else {
+            comm[2] = (double)counts[0];
+            comm[3] = (double)counts[1];
+        }
         scal[0] = sh[512];  // sum (V^2 - V)^2 (V is replicated: not all-reduced)
         counts[0] = 0ull;
         counts[1] = 0ull;
@@ -146,13 +158,25 @@ __global__ __launch_bounds__(256) void gather_kernel(const double* __restrict__ 
                                                       const double* __restrict__ partV, int nbV,
                                                       unsigned long long* __restrict__ counts,
                                                       double* __restrict__ comm, double* __restrict__ scal,
-                                                      const int32_t* __restrict__ stop) {
+                                                      const int32_t* __restrict__ stop, int delta) {
     if (stop && *stop != 0) {   // after the stop nothing rebuilds the exchange block, but a row-sharded run keeps all-reducing it until the
         if (threadIdx.x < 8) comm[threadIdx.x] = 0.0;   // host notices: zeros stay zeros (the values of the last row are in the log)
         return;
     }
     __shared__ double sh[768];
-    gather_body(partU, nbU, partV, nbV, counts, comm, scal, sh);
+    gather_body(partU, nbU, partV, nbV, counts, comm, scal, sh, delta);
+}
+
+// PREPARE with previous words: the full count has just run; the words it counted become the previous ones and the running totals
+// start from zero (the gather adds the full count to them)
+__global__ __launch_bounds__(256) void rebase_cover_kernel(const uint64_t* __restrict__ ubits, uint64_t* __restrict__ ubits_prev, int64_t m_pad,
+                                                            const uint64_t* __restrict__ vbits, uint64_t* __restrict__ vbits_prev, int64_t n_pad,
+                                                            unsigned long long* __restrict__ counts, const int32_t* __restrict__ stop) {
+    if (stop && *stop != 0) return;
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    for (int64_t i = i0; i < m_pad; i += step) ubits_prev[i] = ubits[i];
+    for (int64_t i = i0; i < n_pad; i += step) vbits_prev[i] = vbits[i];
+    if (i0 < 2) counts[2 + i0] = 0ull;
 }
 
 __global__ __launch_bounds__(256) void zero_mae_kernel(double* comm, const int32_t* stop) {
@@ -166,7 +190,8 @@ __device__ __forceinline__ void finalize_body(const bmf_penalty_state& st, int i
     const int sflag = *st.stop;
     if (sflag != 0 && iter > sflag) return;  // rows after the stop iteration do not exist in the reference
     if (do_gather && sflag == 0)
-        gather_body(st.partU, (int)(st.m_pad / 128), st.partV, (int)(st.n_pad / 128), st.counts, st.comm, st.scal, sh);
+        gather_body(st.partU, (int)(st.m_pad / 128), st.partV, (int)(st.n_pad / 128), st.counts, st.comm, st.scal, sh,
+                    st.ubits_prev != nullptr && !st.updates_only);
     const int kk = st.kp * st.kp;
     const double* GU = st.comm + 8;
     double b = 0.0;
@@ -279,6 +304,7 @@ static int check_state(const bmf_penalty_state* st, const char* who) {
                     st->gram_slabs && st->GU && st->GV && st->comm && st->GV64 && st->partU && st->partV && st->scal &&
                     st->ubits && st->ucolbits && st->vbits && st->vcolbits && st->counts && st->log && st->stop,
                 "%s: null device pointer in state", who);
+    BMF_REQUIRE((st->ubits_prev == nullptr) == (st->vbits_prev == nullptr), "%s: ubits_prev and vbits_prev must be both null or both set", who);
     BMF_REQUIRE(st->splits_xv >= 1 && st->splits_xtu >= 1, "%s: splits must be >= 1", who);
     BMF_REQUIRE(st->nred_blocks == 0 || st->nred_blocks == 1 || (st->nred_blocks == 2 && st->kp == 64 && st->panel_kind == BMF_PANEL_I8),
                 "%s: nred_blocks must be 0 / 1, or 2 with kp == 64 and BMF_PANEL_I8", who);
@@ -345,6 +371,8 @@ static int sweep(const bmf_penalty_state* st, int mode, double reg, hipStream_t 
     // fp16 / int8 panels need the column maxima of the whole updated factor, so they are built after the epilogue (which
     // then builds no panel of its own: terms = 0)
     const int epi_terms = (f16 || i8) ? 0 : st->terms;
+    // the Boolean cover as running totals + the change per update (bmf_penalty_state.ubits_prev) instead of a full count per sweep
+    const bool delta = st->ubits_prev && !st->updates_only;
 
     if (phase & SWEEP_HEAD) {
         bmf_epilogue_args ev = {};
@@ -371,6 +399,11 @@ static int sweep(const bmf_penalty_state* st, int mode, double reg, hipStream_t 
                                             nullptr, 0, 0, nullptr, nullptr));
             BMF_TRY(bmf_reduce_slabs(st->gram_slabs, kk, st->gram_blocks, kk, st->GV, st->GV64, s));
         }
+        // column pass of the cover change: the columns whose vbits word the V epilogue changed, against U's bit-columns, which are
+        // still the old ones here (the U epilogue below rewrites them).  It also saves U's old words for the row pass.
+        if (delta && mode != BMF_MODE_PREPARE)
+            BMF_TRY(bmf_cover_delta_launch(st->XTbits, st->ldxt, st->m_pad / 32, st->n_pad, st->vbits, st->vbits_prev, st->ucolbits, st->lduc, kp,
+                                           st->counts, st->ubits, st->ubits_prev, st->m_pad, stop, s));
 
         bmf_timer_begin(s);
         if (i8)
@@ -411,9 +444,19 @@ static int sweep(const bmf_penalty_state* st, int mode, double reg, hipStream_t 
         }
     }
     if (phase & SWEEP_SCALARS) {
-        if (!st->updates_only)
+        if (delta && mode != BMF_MODE_PREPARE) {
+            // row pass: the rows whose ubits word changed, against V's new bit-columns; saves V's words for the next column pass
+            BMF_TRY(bmf_cover_delta_launch(st->Xbits, st->ldx, st->n_pad / 32, st->m_pad, st->ubits, st->ubits_prev, st->vcolbits, st->ldvc, kp,
+                                           st->counts, st->vbits, st->vbits_prev, st->n_pad, stop, s));
+        } else if (!st->updates_only) {
             BMF_TRY(bmf_cover_launch(st->Xbits, st->m_pad, st->ldx, st->n_pad / 32, st->ubits, st->vcolbits, st->ldvc, kp, st->counts,
                                      stop, s));
+            if (delta) {
+                BMF_LAUNCH(rebase_cover_kernel, dim3(64), dim3(256), 0, s, st->ubits, st->ubits_prev, st->m_pad, st->vbits, st->vbits_prev, st->n_pad,
+                           st->counts, stop);
+                BMF_LAUNCH_CHECK();
+            }
+        }
         if (st->with_mae && !st->updates_only) {
             const bool one_product = st->m_pad * st->n_pad >= (1 << 24);   // then the operand conversion zeroes comm[4], comm[5] itself
             if (!(st->mae_ws && one_product)) BMF_LAUNCH(zero_mae_kernel, dim3(1), dim3(64), 0, s, st->comm, stop);
@@ -429,7 +472,7 @@ static int sweep(const bmf_penalty_state* st, int mode, double reg, hipStream_t 
         }
         if (!gather_in_finalize)
             BMF_LAUNCH(gather_kernel, dim3(1), dim3(256), 0, s, st->partU, (int)(st->m_pad / 128), st->partV,
-                               (int)(st->n_pad / 128), st->counts, st->comm, st->scal, stop);
+                               (int)(st->n_pad / 128), st->counts, st->comm, st->scal, stop, delta ? 1 : 0);
         BMF_LAUNCH_CHECK();
     }
     if (!(phase & SWEEP_XTU)) return BMF_OK;

@@ -8,6 +8,11 @@
 // walks the set bits of that row's k-bit word on the scalar unit (the word is wave-uniform) and ORs the
 // selected bit-columns 128 bits per lane; TP/FP are popcounts against the X bits.  Integer arithmetic: exact.
 // Cost is data dependent: popcount(ubits[i]) LDS reads per row-chunk instead of k.
+//
+// The MU fit loop does not recount every iteration: TP and |P| are functions of the thresholded factors alone, and the product can
+// only change in a row whose ubits word changed or a column whose vbits word changed.  cover_delta_kernel (below) counts the change
+// over those rows / columns only, in two launches per iteration (columns with U fixed at its old bits, then rows with V at its new
+// bits); the full count runs once, in the PREPARE sweep, and for every caller that keeps no previous words.
 #include "common.h"
 
 #include <algorithm>
@@ -297,6 +302,236 @@ __global__ __launch_bounds__(1024) void cover_wide_kernel(const uint32_t* __rest
     }
 }
 
+// The CHANGE of the same two counts when the k-bit words of some rows change and the bit-columns stay as they are:
+//   counts[0] += sum_i |X_i & P(new_i)| - |X_i & P(old_i)|,  counts[1] += the same for |~X_i & P|,  P(u) = OR_{l in u} colbits_l,
+// over the rows whose word differs from rowbits_prev ("dirty" rows); every other row contributes what it did before and is not
+// read.  The fit loop keeps running totals and calls this twice per iteration -- on X^T with V's words against U's OLD bit-columns
+// (right after the V update), and on X with U's words against V's NEW bit-columns (after the U update): the two differences
+// telescope to TP(U_t, V_t) - TP(U_{t-1}, V_{t-1}), integers, exact.  Built like cover_wide_kernel (a chunk of <= 640 words of all
+// bit-columns in LDS, 16 waves, one row per wave at a time), but
+//   - the waves find the block's dirty rows first (lane j compares the two words of a row, one ballot per 64 rows), deal them out
+//     among themselves in turn and walk only those; the X words of the next dirty row are in flight while the current one is counted;
+//   - a dirty row walks its factor bits in three parts -- the bits both words share once, then those only the new and only the old
+//     word has (a word usually changes in a bit or two: popc(new | old) LDS reads per segment, not popc(new) + popc(old)) -- and adds
+//     signed differences;
+//   - a block none of whose rows is dirty leaves before it fills the LDS, and one with a few dirty rows fetches only the bit-columns
+//     their words name (160 KiB per block otherwise);
+//   - any words % 4 == 0 is served by the one instantiation: lanes and segments beyond the chunk are masked, not specialised away
+//     (the work is proportional to the dirty rows, not to the matrix, so the narrow shapes need no kernel of their own).
+// Several chunk columns scan the same rows, so the kernel never writes rowbits_prev.  The optional copy (copy_dst[i] = copy_src[i],
+// i < copy_n, by the first threads of the grid) refreshes the OTHER orientation's previous words, which this launch does not read.
+// The block totals are signed; they are added to the 64-bit counters as two's complement, which wraps to the right sum.
+__global__ __launch_bounds__(1024) void cover_delta_kernel(const uint32_t* __restrict__ X, int64_t ldx, int64_t words, int chunk_words,
+                                                            const uint64_t* __restrict__ rowbits, const uint64_t* __restrict__ rowbits_prev,
+                                                            const uint32_t* __restrict__ colbits, int64_t ldcb, int kp, int64_t rows_pad,
+                                                            int rows_per_block, unsigned long long* __restrict__ counts,
+                                                            const uint64_t* __restrict__ copy_src, uint64_t* __restrict__ copy_dst, int64_t copy_n,
+                                                            const int32_t* __restrict__ stop) {
+    if (stop && *stop != 0) return;
+    constexpr int CW = 640, NWV = 16, NS = 3;   // words of a bit-column in LDS; waves per block; segments: 256 + 256 + 128 words
+    __shared__ __attribute__((aligned(16))) uint32_t vt[BMF_MAX_KP * CW];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t w0 = (int64_t)blockIdx.x * chunk_words;
+    const int nw = (int)min((int64_t)chunk_words, words - w0);   // multiple of 4, <= CW
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
+    const int64_t r1 = min(r0 + rows_per_block, rows_pad);
+
+    if (copy_n > 0) {
+        const int64_t nthreads = (int64_t)gridDim.x * gridDim.y * 1024;
+        for (int64_t i = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 1024 + threadIdx.x; i < copy_n; i += nthreads) copy_dst[i] = copy_src[i];
+    }
+
+    // Which bit-columns the block's dirty rows use in either word (a block-wide OR through two words of vt: the kernel's 160 KiB
+    // leave no room for the scratch of __syncthreads_or).  Clean block: nothing to add, and the bit-column chunk is not fetched.
+    unsigned long long need = 0ull;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += 1024) {
+        const unsigned long long a_ = rowbits[r], b_ = rowbits_prev[r];
+        if (a_ != b_) need |= a_ | b_;
+    }
+    if (threadIdx.x < 2) vt[threadIdx.x] = 0u;
+    __syncthreads();
+    if (need) {
+        atomicOr(&vt[0], (unsigned)need);
+        atomicOr(&vt[1], (unsigned)(need >> 32));
+    }
+    __syncthreads();
+    need = ((unsigned long long)vt[1] << 32) | vt[0];
+    __syncthreads();   // (everyone has read the words before the fill overwrites them)
+    if (need == 0ull) return;
+
+    // LDS fill, 16-byte pieces (columns >= kp and words >= nw read as zero).  Few columns needed (a handful of dirty rows: most launches
+    // of a long fit): only those, six columns per trip -- the other columns of vt are never read.  Otherwise all kp columns x CW words.
+    {
+        constexpr int PPC = CW / 4;                // pieces per column
+        constexpr int PIECES = BMF_MAX_KP * PPC;   // 10240 = 10 x 1024
+        const int nneed = __builtin_popcountll(need);
+        if (nneed <= 12) {
+            const int slot = (int)threadIdx.x / PPC, pw = ((int)threadIdx.x % PPC) * 4;
+            u32x4 v[2];
+            int col[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                unsigned long long m_ = need;
+                for (int i = 0; i < 6 * q + slot && m_; ++i) m_ &= m_ - 1;
+                col[q] = (slot < 6 && m_) ? __builtin_ctzll(m_) : -1;
+                v[q] = (col[q] >= 0 && col[q] < kp && pw < nw) ? *reinterpret_cast<const u32x4*>(colbits + (int64_t)col[q] * ldcb + w0 + pw) : u32x4{0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                if (col[q] >= 0) *reinterpret_cast<u32x4*>(&vt[col[q] * CW + pw]) = v[q];
+        } else {
+            for (int base = 0; base < PIECES; base += 5 * 1024) {
+                u32x4 v[5];
+#pragma unroll
+                for (int q = 0; q < 5; ++q) {
+                    const int p = base + q * 1024 + (int)threadIdx.x;
+                    const int l = p / PPC, pw = (p % PPC) * 4;
+                    v[q] = (l < kp && pw < nw) ? *reinterpret_cast<const u32x4*>(colbits + (int64_t)l * ldcb + w0 + pw) : u32x4{0u, 0u, 0u, 0u};
+                }
+#pragma unroll
+                for (int q = 0; q < 5; ++q) *reinterpret_cast<u32x4*>(&vt[4 * (base + q * 1024 + (int)threadIdx.x)]) = v[q];
+            }
+        }
+    }
+    __syncthreads();
+
+    // lane's word offset inside the chunk, per segment (4 words per lane, 2 in the last), and whether those words exist; a segment
+    // wholly beyond the chunk is skipped by the whole wave
+    int soff[NS];
+    bool son[NS];
+#pragma unroll
+    for (int sg = 0; sg < NS; ++sg) {
+        const int o = 256 * sg + (sg < 2 ? 4 : 2) * lane;
+        son[sg] = o < nw;
+        soff[sg] = son[sg] ? o : 0;
+    }
+    const int nseg = (nw + 255) / 256;   // wave-uniform, 1..3
+
+    // pd |= P(u) over this lane's words: two set bits per trip; a missing second bit re-reads the first column (pd | v = pd then)
+    auto add_product = [&](unsigned long long u, u32x4 (&pd)[NS]) {
+        while (u) {
+            const int l0 = __builtin_ctzll(u);
+            u &= u - 1;
+            const int l1 = u ? __builtin_ctzll(u) : l0;
+            u &= u - 1;
+            const uint32_t* c0 = vt + l0 * CW;
+            const uint32_t* c1 = vt + l1 * CW;
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg) {
+                if (sg >= nseg) continue;
+                if (sg < 2) {
+                    pd[sg] |= *reinterpret_cast<const u32x4*>(c0 + soff[sg]) | *reinterpret_cast<const u32x4*>(c1 + soff[sg]);
+                } else {
+                    const u32x2 v0 = *reinterpret_cast<const u32x2*>(c0 + soff[sg]);
+                    const u32x2 v1 = *reinterpret_cast<const u32x2*>(c1 + soff[sg]);
+                    pd[sg][0] |= v0[0] | v1[0];
+                    pd[sg][1] |= v0[1] | v1[1];
+                }
+            }
+        }
+#pragma unroll
+        for (int sg = 0; sg < NS; ++sg)
+            if (!son[sg]) pd[sg] = u32x4{0u, 0u, 0u, 0u};   // lanes beyond the chunk re-read words 0..: mask them out
+    };
+
+    // The dirty rows of the block are dealt to its 16 waves in turn (the k-th dirty row to wave k % 16), so that every wave counts the
+    // same number of them wherever they lie.  Every wave scans all the block's words, 8 groups of 64 rows at a time: one ballot per
+    // group finds the dirty rows, a prefix count ranks them, and the wave keeps its own -- row number and the two words -- one per
+    // lane slot of five registers (at most 512 / 16 = 32 per scan).  It then walks that list, the X words of the next entry in flight
+    // while the current one is counted.
+    constexpr int SCAN = 8;
+    unsigned tpn = 0, tpo = 0, ppn = 0, ppo = 0;   // |X & P(new)|, |X & P(old)|, |P(new)|, |P(old)| (each a popcount-accumulate)
+    const int nrows = (int)(r1 - r0);   // a multiple of 64
+    const uint32_t* xb = X + r0 * ldx + w0;
+    int rank0 = 0;   // dirty rows of the block before the current group (wave-uniform)
+    for (int base = 0; base < nrows; base += 64 * SCAN) {
+        unsigned long long un[SCAN], uo[SCAN];
+#pragma unroll
+        for (int g = 0; g < SCAN; ++g) {
+            const int row = min(base + 64 * g + lane, nrows - 1);
+            un[g] = rowbits[r0 + row];
+            uo[g] = rowbits_prev[r0 + row];
+        }
+        int l_row = 0, l_nlo = 0, l_nhi = 0, l_olo = 0, l_ohi = 0, cnt = 0;
+#pragma unroll
+        for (int g = 0; g < SCAN; ++g) {
+            const bool d_ = base + 64 * g < nrows && un[g] != uo[g];   // (whole groups: nrows % 64 == 0)
+            const unsigned long long mask = __ballot(d_);
+            const int rk = rank0 + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+            unsigned long long mine = __ballot(d_ && (rk & (NWV - 1)) == wave);
+            rank0 += __builtin_popcountll(mask);
+            while (mine) {
+                const int j = __builtin_ctzll(mine);
+                mine &= mine - 1;
+                const bool slot = lane == cnt;   // (the uniform value into lane `cnt` of the list register)
+                l_row = slot ? base + 64 * g + j : l_row;
+                l_nlo = slot ? __builtin_amdgcn_readlane((int)(unsigned)un[g], j) : l_nlo;
+                l_nhi = slot ? __builtin_amdgcn_readlane((int)(unsigned)(un[g] >> 32), j) : l_nhi;
+                l_olo = slot ? __builtin_amdgcn_readlane((int)(unsigned)uo[g], j) : l_olo;
+                l_ohi = slot ? __builtin_amdgcn_readlane((int)(unsigned)(uo[g] >> 32), j) : l_ohi;
+                ++cnt;
+            }
+        }
+        if (cnt == 0) continue;
+        u32x4 x_cur[NS], x_nxt[NS];
+        // (non-temporal: the words of X are used once per launch and should not displace the factor panels in L2)
+        auto load_row = [&](int t, u32x4 (&dst)[NS]) {
+            const uint32_t* xr = xb + (int64_t)__builtin_amdgcn_readlane(l_row, t) * ldx;
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg) {
+                dst[sg] = u32x4{0u, 0u, 0u, 0u};
+                if (sg >= nseg) continue;
+                if (sg < 2) dst[sg] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(xr + soff[sg]));
+                else {
+                    const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xr + soff[sg]));
+                    dst[sg] = u32x4{v[0], v[1], 0u, 0u};
+                }
+            }
+        };
+        load_row(0, x_cur);
+        for (int t = 0; t < cnt; ++t) {
+            load_row(t + 1 < cnt ? t + 1 : t, x_nxt);   // the last entry re-reads itself (keeps the loop uniform)
+            // (readlane returns int: through unsigned, or a set bit 31 of the low half would sign-extend over the high half)
+            const unsigned wn_lo = __builtin_amdgcn_readlane(l_nlo, t), wn_hi = __builtin_amdgcn_readlane(l_nhi, t);
+            const unsigned wo_lo = __builtin_amdgcn_readlane(l_olo, t), wo_hi = __builtin_amdgcn_readlane(l_ohi, t);
+            const unsigned long long wn = ((unsigned long long)wn_hi << 32) | wn_lo, wo = ((unsigned long long)wo_hi << 32) | wo_lo;
+            u32x4 pn[NS], po[NS];
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg) pn[sg] = u32x4{0u, 0u, 0u, 0u};
+            add_product(wn & wo, pn);
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg) po[sg] = pn[sg];
+            add_product(wn & ~wo, pn);
+            add_product(wo & ~wn, po);
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    tpn += __popc(x_cur[sg][q] & pn[sg][q]);
+                    tpo += __popc(x_cur[sg][q] & po[sg][q]);
+                    ppn += __popc(pn[sg][q]);
+                    ppo += __popc(po[sg][q]);
+                }
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg) x_cur[sg] = x_nxt[sg];
+        }
+    }
+    // one atomic pair per block (see cover_kernel); the bit-columns are dead: their LDS is the reduction buffer
+    int tp = (int)wave_sum(tpn - tpo);   // signed, two's complement through the unsigned sum
+    int pp = (int)wave_sum(ppn - ppo);
+    __syncthreads();
+    if (lane == 0) { vt[wave] = (unsigned)tp; vt[NWV + wave] = (unsigned)pp; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        long long t = 0, a_ = 0;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) { t += (int)vt[w]; a_ += (int)vt[NWV + w]; }
+        const long long val = threadIdx.x == 0 ? t : a_ - t;   // change of TP, of FP = |P| - TP
+        if (val) atomicAdd(&counts[threadIdx.x], (unsigned long long)val);
+    }
+}
+
 // Materialise the Boolean product as bits: out[i][w] = OR_{l in rowbits[i]} colbits[l][w]  (the X_pd the reference builds
 // with csr @ csr, PyBMF/utils/common.py:147-149).  Thread per (row, word); used once at the end of fit(), not in the loop.
 __global__ __launch_bounds__(256) void product_bits_kernel(const uint64_t* __restrict__ rowbits, int64_t rows,
@@ -426,6 +661,40 @@ extern "C" int bmf_cover_count(const uint32_t* Xbits, int64_t rows_pad, int64_t 
     BMF_REQUIRE(kp >= 1 && kp <= BMF_MAX_KP, "bmf_cover_count: kp must be 1..64");
     BMF_REQUIRE(bmf_aligned16(Xbits), "bmf_cover_count: Xbits must be 16-byte aligned");
     return bmf_cover_launch(Xbits, rows_pad, ldx, words, rowbits, colbits, ldcb, kp, counts, stop, (hipStream_t)stream);
+}
+
+int bmf_cover_delta_launch(const uint32_t* bits, int64_t ld, int64_t words, int64_t rows_pad, const uint64_t* rowbits,
+                           const uint64_t* rowbits_prev, const uint32_t* colbits, int64_t ldcb, int kp, unsigned long long* counts,
+                           const uint64_t* copy_src, uint64_t* copy_dst, int64_t copy_n, const int32_t* stop, hipStream_t s) {
+    // chunk columns of <= 640 words (a multiple of 128 from 128 words on, as bmf_cover_launch cuts them), one workgroup per CU
+    const int chunks_w = (int)((words + 639) / 640);
+    const int64_t per = (words + chunks_w - 1) / chunks_w;
+    const int cw = (int)(words >= 128 ? (per + 127) / 128 * 128 : words);   // a multiple of 4
+    const int cus = bmf_cu_count_current();
+    int64_t groups = cus / chunks_w > 0 ? cus / chunks_w : 1;
+    const int64_t units = rows_pad / 64;
+    if (groups > units) groups = units;
+    const int rows_per_block = (int)(((units + groups - 1) / groups) * 64);
+    groups = (rows_pad + rows_per_block - 1) / rows_per_block;
+    BMF_LAUNCH(cover_delta_kernel, dim3((unsigned)chunks_w, (unsigned)groups), dim3(1024), 0, s, bits, ld, words, cw, rowbits, rowbits_prev, colbits,
+               ldcb, kp, rows_pad, rows_per_block, counts, copy_src, copy_dst, copy_n, stop);
+    BMF_LAUNCH_CHECK();
+    return BMF_OK;
+}
+
+extern "C" int bmf_cover_delta(const uint32_t* bits, int64_t ld, int64_t words, int64_t rows_pad, const uint64_t* rowbits,
+                               const uint64_t* rowbits_prev, const uint32_t* colbits, int64_t ldcb, int kp, unsigned long long* counts,
+                               const uint64_t* copy_src, uint64_t* copy_dst, int64_t copy_n, const int32_t* stop, void* stream) {
+    BMF_REQUIRE(bits && rowbits && rowbits_prev && colbits && counts, "bmf_cover_delta: null pointer");
+    BMF_REQUIRE(rows_pad > 0 && rows_pad % 64 == 0, "bmf_cover_delta: rows_pad must be a positive multiple of 64");
+    BMF_REQUIRE(words >= 4 && words % 4 == 0 && ld >= words && ld % 4 == 0, "bmf_cover_delta: words/ld must be multiples of 4, ld >= words >= 4");
+    BMF_REQUIRE(ldcb >= words && ldcb % 4 == 0, "bmf_cover_delta: ldcb must be >= words and a multiple of 4");
+    BMF_REQUIRE(bmf_aligned16(bits) && bmf_aligned16(colbits), "bmf_cover_delta: bits and colbits must be 16-byte aligned");
+    BMF_REQUIRE(kp >= 1 && kp <= BMF_MAX_KP, "bmf_cover_delta: kp must be 1..64");
+    BMF_REQUIRE(copy_n >= 0 && (copy_n == 0 || (copy_src && copy_dst)), "bmf_cover_delta: copy_n > 0 needs copy_src and copy_dst");
+    BMF_REQUIRE(copy_n == 0 || (copy_dst != rowbits && copy_dst != rowbits_prev), "bmf_cover_delta: the copy must not overwrite the words this launch compares");
+    return bmf_cover_delta_launch(bits, ld, words, rows_pad, rowbits, rowbits_prev, colbits, ldcb, kp, counts, copy_src, copy_dst, copy_n, stop,
+                                  (hipStream_t)stream);
 }
 
 extern "C" int bmf_boolean_product_bits(const uint64_t* rowbits, int64_t rows, const uint32_t* colbits, int64_t ldcb, int kp,

@@ -153,7 +153,8 @@ class OneStep:
     def __init__(self, X, U, V, mode=L.MODE_PENALTY, device=DEFAULT_DEVICE, terms=3):
         U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
         self.B = BitMatrix(X, device)
-        self.eng = MUEngine(self.B, k=U.shape[1], mode=mode, terms=terms, with_mae=False, tol=-1.0, min_diff=-1.0, max_iter=4)
+        self.eng = MUEngine(self.B, k=U.shape[1], mode=mode, terms=terms, with_mae=False, tol=-1.0, min_diff=-1.0, max_iter=4,
+                            cover_delta=False)   # (single steps through the epilogue itself: nothing keeps running cover totals valid)
         self.eng.load_factors(U, V)
 
     def _epilogue(self, which: str, reg: float):

@@ -218,7 +218,7 @@ class MUEngine(ExchangeLoop):
 
     def __init__(self, X: BitMatrix, k: int, mode: int = L.MODE_PENALTY, terms: int = 3, with_mae: bool = True,
                  thr=(0.5, 0.5), tol: float = 0.01, min_diff: float = 0.0, max_iter: int = 100, sharded: bool = False,
-                 group=None, panel: str = "bf16", mae: str = "bf16"):
+                 group=None, panel: str = "bf16", mae: str = "bf16", cover_delta: Optional[bool] = None):
         if not (1 <= k <= L.MAX_KP):
             raise NotImplementedError(f"k={k}: this build supports 1 <= k <= {L.MAX_KP}")
         if panel not in ("bf16", "f16", "i8"):
@@ -275,6 +275,13 @@ class MUEngine(ExchangeLoop):
         self.ubits, self.vbits = z((m_pad,), torch.int64), z((n_pad,), torch.int64)
         self.ucolbits, self.vcolbits = z((kp, m_pad // 32), torch.int32), z((kp, n_pad // 32), torch.int32)
         self.counts = z((4,), torch.int64)
+        # the Boolean cover as running totals: prepare() counts in full, every update adds the change over the rows / columns whose
+        # k-bit word changed (bmf_penalty_state.ubits_prev).  cover_delta=False (or BMF_COVER_DELTA=0, for A/B runs): a full count
+        # over X in every iteration
+        if cover_delta is None:
+            cover_delta = os.environ.get("BMF_COVER_DELTA", "1") != "0"
+        self.cover_delta = bool(cover_delta)
+        self.ubits_prev, self.vbits_prev = (z((m_pad,), torch.int64), z((n_pad,), torch.int64)) if self.cover_delta else (None, None)
         self.log_rows = self.max_iter + 2
         self.log = z((self.log_rows, L.LOG_COLS), torch.float64)
         self.stop = z((1,), torch.int32)
@@ -321,6 +328,8 @@ class MUEngine(ExchangeLoop):
         st.scaleU, st.scaleV, st.panel_ws = self.scaleU.data_ptr(), self.scaleV.data_ptr(), self.panel_ws.data_ptr()
         st.mae_ws = self.mae_ws.data_ptr() if self.mae_ws is not None else None
         st.nred_blocks = self.nred_blocks
+        if self.cover_delta:
+            st.ubits_prev, st.vbits_prev = self.ubits_prev.data_ptr(), self.vbits_prev.data_ptr()
         # (0 = the library's rule on this state; with several ranks the rule is evaluated on the largest shard: same answer everywhere)
         st.exchange_overlap = (2 if lib.bmf_exchange_overlap_rule(int(self.with_mae), self.m_pad_max) else 1) if self.world > 1 else 0
         if panel == "i8":
