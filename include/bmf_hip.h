@@ -871,6 +871,24 @@ int bmf_hyper_eval(const uint32_t* tid, const uint32_t* rs_t, int32_t n, int64_t
 int bmf_hyper_copy(const uint32_t* src, int32_t n_src, const int32_t* src_id, uint32_t* dst, int32_t n_dst, const int32_t* dst_id,
                    int64_t ld, int32_t count, void* stream);
 
+/* ---- HyperPlus: merge trials of hyperrectangles on bit sets (csrc/hyperplus.hip) -----------------------------------------------------
+ * PyBMF/models/HyperPlus.py:100-127, 169-185.  x_t and pd_t are X and the cover transposed as for Hyper (n bit rows of ld = m_pad / 32
+ * words); u_t holds the factors' row sets T as k bit rows of ld words, v their column sets I as k bit rows of ldv = n_pad / 32 words
+ * (ld, ldv multiples of 4, every array 16-byte aligned).  Exact integers, no atomics, no floating point; the budget test and the
+ * savings are host fp64 on these integers.
+ * THE PADDING CONTRACT: bits >= m of every u_t row and bits >= n of every v row are zero.  ~x_t[j] & ~pd_t[j] is all ones in the
+ * padding bits of a row; only T's zero padding keeps them out of new_fp.
+ *
+ * bmf_hyperplus_pairs: for c < count, with (a, b) = pair[2 c], pair[2 c + 1], T = u_t[a] | u_t[b] and I = v[a] | v[b]:
+ *   rec[5 c ..] = { new_fp = the sum over j in I of |T & ~x_t[j] & ~pd_t[j]|, |T|, |I|, |u_t[a] & u_t[b]|, |v[a] & v[b]| } as int64.
+ *   T x I contains both rectangles, so the cover with the pair merged is pd | T x I and its FP is the current FP + new_fp.  A pair
+ *   with an id outside [0, k) or with a == b writes -1 five times.  pair 4-byte, rec 8-byte aligned; 1 <= count <= 2^30; n <= 32 ldv.
+ * bmf_hyperplus_union: u_t[dst] = u_t[a] | u_t[b], v[dst] = v[a] | v[b]; dst may be a or b; ids outside [0, k) are refused.  The
+ *   cover itself is updated with bmf_mebf_apply (pd_t[j] |= T for j in I, with the sums). */
+int bmf_hyperplus_pairs(const uint32_t* u_t, const uint32_t* v, int32_t k, const uint32_t* x_t, const uint32_t* pd_t, int32_t n, int64_t ld,
+                        int64_t ldv, const int32_t* pair, int32_t count, int64_t* rec, void* stream);
+int bmf_hyperplus_union(uint32_t* u_t, uint32_t* v, int32_t k, int64_t ld, int64_t ldv, int32_t a, int32_t b, int32_t dst, void* stream);
+
 /* ---- GreConD+: factor expansion, rebuild and overlap pruning on bit sets (csrc/grecondplus.hip) -----------------------------------
  * PyBMF/models/GreConDPlus.py:131-308.  A bit matrix is `lines` bit rows of ld words, zero padded: row-major (line = row of X, ld = n_pad
  * / 32) or transposed (line = column of X, ld = m_pad / 32).  RS = X & ~PD is the residual, which an expansion holds fixed.  Exact

@@ -267,6 +267,8 @@ SIGNATURES = {
     "bmf_hyper_level": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp]),
     "bmf_hyper_eval": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "bmf_hyper_copy": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _vp]),
+    "bmf_hyperplus_pairs": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "bmf_hyperplus_union": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
     "bmf_expand_counts": (C.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp]),
     "bmf_expand_rec_words": (_i64, [_i32, _i32]),
     "bmf_expand_steps": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
