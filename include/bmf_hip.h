@@ -235,7 +235,10 @@ int bmf_tile_f32(const float* X, int64_t rows_pad, int64_t lda, int64_t red, flo
  *   frag[((((st * 2 + kh) * 4 + u) * NT + nt) * 64 + 32 h + r) * 4 + t] = F[(64 st + 32 kh + 8 u + 4 h + t) * kp + 32 nt + r]. */
 int bmf_frag_f32(const float* F, int64_t rows_pad, int kp, float* frag, void* stream);
 /* out = A . F like bmf_xf_f32, from the tiled copy of A (bmf_tile_f32) and the fragment-ordered factor (bmf_frag_f32 of the
- * red x kp factor); same numbers as bmf_xf_f32 on A and F^T bit for bit. */
+ * red x kp factor); same numbers as bmf_xf_f32 on A and F^T bit for bit.
+ * rows_pad % 128 == 0 (bmf_xf_f32's argument check, shared, although the kernel behind both tiles the rows by 64: an odd count of
+ * 64-row tiles is refused here and taken by the bf3 and resid forms below), red % 64 == 0, out 16-byte aligned, 1 <= splits <= red / 8;
+ * a split whose range of 64-index stages is empty writes a slab of zeros. */
 int bmf_xf_f32_tiled(const float* Atiled, int64_t rows_pad, int64_t red, const float* Ffrag, int kp, float* out,
                      int64_t slab_stride, int splits, void* stream);
 /* The same contraction with the residual sums of the pass folded in (kp == 32): out = A F, and sums[0] += sum |A - G F^T|, sums[1] +=

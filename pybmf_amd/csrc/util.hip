@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256) void make_panel_f16_kernel(const float* __rest
 // (out32 may be the first slab: every element's slabs are read before its sum is written, by the same thread or after a barrier)
 __global__ __launch_bounds__(1024) void reduce_slabs_kernel(const float* slabs, int64_t stride, int count,
                                                              int64_t n, float* out32,
-                                                             double* __restrict__ out64) {
+                                                             double* __restrict__ out64, const int32_t* __restrict__ stop) {
+    if (stop && *stop != 0) return;   // (block-uniform: before the barrier)
     constexpr int NG = 16;  // slab groups per block: 64 outputs x 16 groups = 1024 threads
     __shared__ double sh[NG][64];
     const int o = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -404,20 +405,27 @@ extern "C" int bmf_make_panel_f16(const float* F, int64_t rows_pad, int64_t ldf,
     return bmf_panel_f16_launch(F, rows_pad, ldf, kp, panel, ldp, ws, scale, false, nullptr, (hipStream_t)stream);
 }
 
-extern "C" int bmf_reduce_slabs(const float* slabs, int64_t stride, int count, int64_t n, float* out32, double* out64,
-                                void* stream) {
+// stop (may be NULL): a raised device flag leaves out32 / out64 alone -- for the whole-iteration drivers, whose every launch behind a
+// tripped stopping rule must be a no-op: the slabs then hold whatever their last writer left, not this call's
+int bmf_reduce_slabs_launch(const float* slabs, int64_t stride, int count, int64_t n, float* out32, double* out64, const int32_t* stop,
+                            hipStream_t stream) {
     BMF_REQUIRE(slabs && (out32 || out64), "bmf_reduce_slabs: null pointer");
     BMF_REQUIRE(count >= 1 && n >= 1 && stride >= n, "bmf_reduce_slabs: bad count/n/stride");
-    if (n >= 65536 && n % 4 == 0 && stride % 4 == 0 && bmf_aligned16(slabs) && (!out32 || bmf_aligned16(out32))) {
+    if (!stop && n >= 65536 && n % 4 == 0 && stride % 4 == 0 && bmf_aligned16(slabs) && (!out32 || bmf_aligned16(out32))) {   // (the wide form takes no flag)
         const int64_t n4 = n / 4, blocks = (n4 + 255) / 256;
         BMF_LAUNCH(reduce_slabs_wide_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                           (hipStream_t)stream, slabs, stride, count, n4, out32, out64);
+                           stream, slabs, stride, count, n4, out32, out64);
     } else {
         dim3 grid((unsigned)((n + 63) / 64)), block(1024);
-        BMF_LAUNCH(reduce_slabs_kernel, grid, block, 0, (hipStream_t)stream, slabs, stride, count, n, out32, out64);
+        BMF_LAUNCH(reduce_slabs_kernel, grid, block, 0, stream, slabs, stride, count, n, out32, out64, stop);
     }
     BMF_LAUNCH_CHECK();
     return BMF_OK;
+}
+
+extern "C" int bmf_reduce_slabs(const float* slabs, int64_t stride, int count, int64_t n, float* out32, double* out64,
+                                void* stream) {
+    return bmf_reduce_slabs_launch(slabs, stride, count, n, out32, out64, nullptr, (hipStream_t)stream);
 }
 
 // blockmax != nullptr: kp / 4 extra blocks derive the int8 column scales (see the kernel)

@@ -25,6 +25,8 @@ int bmf_xf_f32_resid_launch(const float* Atiled, int64_t rows_pad, int64_t red, 
 int bmf_xf_f32_bf3_launch(const float* Atiled, int64_t rows_pad, int64_t red, const uint32_t* F3, float* out, int64_t slab_stride, int splits,
                           const int32_t* stop, hipStream_t s);
 int bmf_frag_rows_bf16_launch(const float* F, int64_t rows_pad, int kp, uint32_t* frag, const int32_t* stop, hipStream_t s);
+int bmf_reduce_slabs_launch(const float* slabs, int64_t stride, int count, int64_t n, float* out32, double* out64, const int32_t* stop,
+                            hipStream_t stream);
 int bmf_frag_pair_launch(const float* F, int64_t rows_pad, float* frag, uint32_t* frag_bf, double* zero4, const int32_t* stop, hipStream_t s);
 
 namespace {
@@ -326,7 +328,8 @@ static int fused_update(const bmf_wnmf_real_state* st, bool is_u, int mode, bool
     BMF_LAUNCH(real_update_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
     BMF_LAUNCH_CHECK();
     const int kk = st->kp * st->kp;
-    return bmf_reduce_slabs(st->gram_slabs, kk, blocks, kk, is_u ? st->GU : st->GV, is_u ? st->GU64 : st->GV64, s);
+    // (stop-aware: behind a raised flag the update above has written no slab, and the buffer, shared by the two sides, holds the other side's)
+    return bmf_reduce_slabs_launch(st->gram_slabs, kk, blocks, kk, is_u ? st->GU : st->GV, is_u ? st->GU64 : st->GV64, st->stop, s);
 }
 
 // everything of an iteration after the V update: V^T, V^T V, X V, U (update or, at iteration 0, bookkeeping), U^T, U^T U, X^T U, MAE
