@@ -68,7 +68,8 @@ int bmf_version(void);
 const char* bmf_last_error(void);
 /* sizeof() of the argument structs as THIS library was compiled, so that a binding can refuse a mismatch before the first call
  * (the structs that are passed without a struct_bytes field of their own included): which = 0 bmf_epilogue_args, 1 bmf_palm_args,
- * 2 bmf_penalty_state, 3 bmf_wnmf_real_state, 4 bmf_palm_state, 5 bmf_masked_loop, 6 bmf_masked_side, 7 bmf_link_loop; -1 for an unknown id. */
+ * 2 bmf_penalty_state, 3 bmf_wnmf_real_state, 4 bmf_palm_state, 5 bmf_masked_loop, 6 bmf_masked_side, 7 bmf_link_loop,
+ * 8 bmf_nmf_state; -1 for an unknown id. */
 int bmf_struct_bytes(int which);
 
 /* position of local reduction index cl (0..127) inside its 128-block of a factor panel (host helper) */
@@ -1224,6 +1225,48 @@ int bmf_palm_finish_row(const bmf_palm_state* st, int it, void* stream);
  * inertial term and are never advanced (:96-110).  Everything is enqueued; nothing returns to the host. */
 int bmf_primp_iterate(const bmf_palm_state* st, int it, double l1, double l2, void* stream);
 
+/* ---- coordinate-descent NMF (csrc/nmf_cd.hip): scikit-learn's Frobenius 'cd' solver, PyBMF/models/NMFSklearn.py:38-60 -------------
+ * One call of _update_cdnmf_fast(W, HHt, XHt, permutation = arange(k)) for one factor, in fp64 and in that function's order of
+ * operations: for every row i and t = 0 .. k-1 ascending
+ *     grad = -XHt[i][t];  for r = 0 .. k-1: grad += HHt[t][r] * W[i][r]      (W[i][r] already updated for r < t)
+ *     pg = W[i][t] == 0 ? min(0, grad) : grad;  violation += |pg|
+ *     hess = HHt[t][t];  if (hess != 0) W[i][t] = max(W[i][t] - grad / hess, 0)
+ * F64 (rows_pad x kp, in place) is W, F its fp32 shadow (rewritten), G64 (kp x kp fp64, row-major) is HHt, and XHt[i][t] =
+ * sum_s (double)num[s][i][t] over the `splits` fp32 slabs of the bits GEMM, added in slab order.  Rows >= rows and columns >= k are
+ * padding: their slab and Gram entries are not read, whatever F64 holds there on entry is ignored, F64 / F are written as exact zeros
+ * there and they add nothing to the violation.
+ * blockmax ([rows_pad / 128][kp]): max |F| per 128-row block and column, what bmf_gram_partial_i8 / the digit-plane builder take;
+ * viol ([rows_pad / 128]): the violation of each 128-row block, lanes and waves added in a fixed order (no atomics).
+ * rows_pad % 128 == 0, 1 <= rows <= rows_pad, 1 <= k <= kp, kp in {32, 64}, splits >= 1, slab_stride >= rows_pad * kp and
+ * slab_stride % 4 == 0 (every slab starts 16-byte aligned); F64, F and num 16-byte aligned. */
+int bmf_nmf_cd_sweep(double* F64, float* F, int64_t rows_pad, int32_t rows, int k, int kp, const float* num, int64_t slab_stride,
+                     int splits, const double* G64, float* blockmax, double* viol, void* stream);
+
+typedef struct {
+    int32_t struct_bytes; /* sizeof(bmf_nmf_state): layout check */
+    int32_t m, n, k, kp;
+    int32_t splits_xv, splits_xtu; /* slab slots of X V / X^T U (bmf_xf_bits_i8_slots) */
+    int32_t gram_blocks, log_rows, _pad0;
+    int64_t m_pad, n_pad;
+    const uint32_t* Xtiled;  /* X and X^T as bmf_tile_bits leaves them */
+    const uint32_t* XTtiled;
+    double *U64, *V64;       /* m_pad x kp, n_pad x kp */
+    float *U, *V;            /* their fp32 shadows */
+    int8_t *Upanel, *Vpanel; /* [3][kp][m_pad], [3][kp][n_pad]; Vpanel / scaleV must describe V on entry to an iteration */
+    float *scaleU, *scaleV;  /* 2 * kp floats each */
+    float *wsU, *wsV;        /* (rows_pad / 128) * kp block maxima */
+    float *Mslab, *Nslab;    /* [splits_xv][m_pad][kp], [splits_xtu][n_pad][kp] */
+    float* gram_slabs;       /* [gram_blocks][kp][kp] */
+    float *GU, *GV;          /* kp x kp */
+    double *GU64, *GV64;
+    double *partU, *partV;   /* m_pad / 128, n_pad / 128 violation partials */
+    double* log;             /* log_rows rows of 8 doubles the device can write (pinned host memory) */
+} bmf_nmf_state;
+/* One iteration of _fit_coordinate_descent (sklearn/decomposition/_nmf.py) per call: V^T V, X V, the sweep of U, the digit planes of the
+ * new U; U^T U, X^T U, the sweep of V, the digit planes of the new V.  Words 0 and 1 of log row it % log_rows receive the violations of
+ * the U and of the V sweep.  The stopping rule (violation / violation of iteration 1 <= tol) is the caller's. */
+int bmf_nmf_cd_iterate(const bmf_nmf_state* st, int it, void* stream);
+
 /* ---- rank 64 < k <= 128: what couples the two 64-column blocks of a factor (csrc/wide.hip) --------------------------------------
  * A wider factor is held as two blocks F = [F_0 | F_1] of 64 columns each (every array of the k <= 64 path once per block); the
  * contractions, digit planes and the fp64 epilogue run per block, the epilogue with a precomputed denominator (`den`). */
@@ -1250,7 +1293,7 @@ int bmf_resid_sums_wide(const uint32_t* XTbits, int64_t ldxt, int64_t m_pad, int
 
 /* ---- kernel timing (bench.py roofline leg) ----------------------------------------------------------------------- */
 
-/* When enabled, bmf_xf_bits launches made through bmf_penalty_update are bracketed by hipEvents on `stream`
+/* When enabled, bmf_xf_bits launches made through bmf_penalty_update (and the two sweep launches of bmf_nmf_cd_iterate) are bracketed by hipEvents on `stream`
  * (created by bmf_timer_enable, which therefore must not be called during graph capture).  bmf_timer_read
  * synchronises the events and returns the number of timed launches and their total milliseconds. */
 int bmf_timer_enable(int max_launches);

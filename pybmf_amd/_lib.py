@@ -98,6 +98,17 @@ class PalmState(C.Structure):
     ]
 
 
+class NmfState(C.Structure):
+    """bmf_nmf_state"""
+    _fields_ = [
+        ("struct_bytes", _i32), ("m", _i32), ("n", _i32), ("k", _i32), ("kp", _i32), ("splits_xv", _i32), ("splits_xtu", _i32),
+        ("gram_blocks", _i32), ("log_rows", _i32), ("_pad0", _i32), ("m_pad", _i64), ("n_pad", _i64), ("Xtiled", _vp), ("XTtiled", _vp),
+        ("U64", _vp), ("V64", _vp), ("U", _vp), ("V", _vp), ("Upanel", _vp), ("Vpanel", _vp), ("scaleU", _vp), ("scaleV", _vp),
+        ("wsU", _vp), ("wsV", _vp), ("Mslab", _vp), ("Nslab", _vp), ("gram_slabs", _vp), ("GU", _vp), ("GV", _vp), ("GU64", _vp), ("GV64", _vp),
+        ("partU", _vp), ("partV", _vp), ("log", _vp),
+    ]
+
+
 class WnmfRealState(C.Structure):
     """bmf_wnmf_real_state"""
     _fields_ = [
@@ -310,6 +321,8 @@ SIGNATURES = {
     "bmf_palm_row_lag": (C.c_int, [_vp]),
     "bmf_palm_finish_row": (C.c_int, [_vp, C.c_int, _vp]),
     "bmf_primp_iterate": (C.c_int, [_vp, C.c_int, _f64, _f64, _vp]),
+    "bmf_nmf_cd_sweep": (C.c_int, [_vp, _vp, _i64, _i32, C.c_int, C.c_int, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp]),
+    "bmf_nmf_cd_iterate": (C.c_int, [C.POINTER(NmfState), C.c_int, _vp]),
     "bmf_timer_stride": (C.c_int, [C.c_int]),
     "bmf_timer_enable": (C.c_int, [C.c_int]),
     "bmf_timer_read": (C.c_int, [C.POINTER(C.c_int), C.POINTER(_f64)]),
@@ -337,7 +350,7 @@ def _load():
     # the ctypes mirrors against the library's own sizeof(): a header / binding mismatch fails here, not as a corrupted launch
     if lib.bmf_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.bmf_version()}, this binding was written for {ABI_VERSION} (rebuild the library)")
-    for which, mirror in enumerate((EpilogueArgs, PalmArgs, PenaltyState, WnmfRealState, PalmState, MaskedLoop, MaskedSide, LinkLoop)):
+    for which, mirror in enumerate((EpilogueArgs, PalmArgs, PenaltyState, WnmfRealState, PalmState, MaskedLoop, MaskedSide, LinkLoop, NmfState)):
         if lib.bmf_struct_bytes(which) != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: sizeof({mirror.__doc__}) is {lib.bmf_struct_bytes(which)} in the library, {C.sizeof(mirror)} in the binding")
     return lib

@@ -27,6 +27,7 @@ extern "C" int bmf_struct_bytes(int which) {
         case 5: return (int)sizeof(bmf_masked_loop);
         case 6: return (int)sizeof(bmf_masked_side);
         case 7: return (int)sizeof(bmf_link_loop);
+        case 8: return (int)sizeof(bmf_nmf_state);
         default: return -1;
     }
 }

@@ -17,5 +17,6 @@ from .MEBF import MEBF
 from .Panda import Panda
 from .Hyper import Hyper
 from .HyperPlus import HyperPlus
+from .NMFSklearn import NMFSklearn
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus", "NMFSklearn"]
