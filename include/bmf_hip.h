@@ -752,6 +752,28 @@ int bmf_masked_thresh64_k(const int64_t* ptr, const int32_t* idx, const float* v
                           const int64_t* seg_beg, int32_t nseg, const double* Us, const double* dUs, const double* Vs, const double* dVs,
                           int kp, int kcols, double* partial, int32_t partial_blocks, double* out, void* stream);
 
+/* The fp64 thresholding objective at a rank 64 < k <= 128 (csrc/thresh_wide.hip): transformed factors of 128 columns, a lane holds two
+ * adjacent columns.  Every function below refuses k <= 64 (the entry points above serve that) and k > 128.
+ * Trace form (the all-ones mask): arguments, workspace rule (zero-filled ONCE by the caller, 16-byte aligned) and output protocol are
+ * those of bmf_thresh_trace64 -- out[4 p] = seq behind (2 F, dF_u, dF_v) of pair p, out[4 n_pairs] = seq written last, each behind a
+ * system-scope fence; ldf >= k, columns >= k and rows >= m / n of U64 / V64 are never read.  Up to
+ * bmf_thresh_trace_wide_max_pairs(k) = 8 pairs per call.  The Gram matrices are 128 x 128, summed over at most 32 row chunks per factor
+ * whatever its length, so the workspace is 2 pairs (m + n + 2) 128 doubles + 3 pairs (8 m + 64) + at most 2^21 doubles per pair.
+ * Fixed-order sums, no floating-point atomics; 2 F is the same bit pattern with and without the gradient. */
+int bmf_thresh_trace_wide_max_pairs(int k);
+int64_t bmf_thresh_trace_wide_work(int32_t m, int32_t n, int k, int max_pairs);
+int bmf_thresh_trace_wide(const int32_t* seg_row, const int64_t* seg_beg, const int32_t* seg_len, int32_t nseg, const int32_t* idx, int32_t m,
+                          int32_t n, const double* U64, const double* V64, int64_t ldf, int k, const double* uv_host, int32_t n_pairs,
+                          double lamda, double sum_x, int want_grad, double* work, double* out_host, double seq, void* stream);
+/* Observed cells (W = 'mask' / weights): F is rows_pad x 128 fp64 with k real columns; S, D (D may be NULL): rows_pad x 128, exact zero
+ * in the padding.  bmf_masked_thresh64_wide: cell lists, segment tables, partial / partial_blocks and the three outputs of
+ * bmf_masked_thresh64_k on such factors (16-byte aligned); a cell's dot product runs over all 128 columns before its residual is formed. */
+int bmf_thresh_transform64_wide(const double* F, int64_t rows_pad, int32_t rows, int k, double x, double lamda, double* S, double* D,
+                                void* stream);
+int bmf_masked_thresh64_wide(const int64_t* ptr, const int32_t* idx, const float* val, const float* wgt, const int32_t* seg_row,
+                             const int64_t* seg_beg, int32_t nseg, const double* Us, const double* dUs, const double* Vs, const double* dVs,
+                             int k, double* partial, int32_t partial_blocks, double* out, void* stream);
+
 /* ---- FastStep: the logistic loss of one factor, for the projected line search (csrc/faststep.hip) ---------------------------
  * PyBMF/models/FastStep.py:147-211.  With M = 2 X - 1, S = U V^T where column k of the factors is replaced by the candidate (u, v),
  * and a = -M o (S - tau):

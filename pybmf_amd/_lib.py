@@ -255,7 +255,12 @@ SIGNATURES = {
     "bmf_thresh_transform64": (C.c_int, [_vp, _i64, _i32, C.c_int, C.c_int, _f64, _f64, _vp, _vp, _vp]),
     "bmf_masked_thresh64": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, C.c_int, _vp, _i32, _vp, _vp]),
     "bmf_masked_thresh64_k": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _i32, _vp, _vp]),
-    "bmf_faststep_base": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, C.c_int, C.c_int, C.c_int, _f64, _vp, _vp]),
+    "bmf_thresh_trace_wide_max_pairs": (C.c_int, [C.c_int]),
+    "bmf_thresh_trace_wide_work": (_i64, [_i32, _i32, C.c_int, C.c_int]),
+    "bmf_thresh_trace_wide": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, C.c_int, _vp, _i32, _f64, _f64, C.c_int, _vp, _vp, _f64, _vp]),
+    "bmf_thresh_transform64_wide": (C.c_int, [_vp, _i64, _i32, C.c_int, _f64, _f64, _vp, _vp, _vp]),
+    "bmf_masked_thresh64_wide": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, C.c_int, _vp, _i32, _vp, _vp]),
+    "bmf_faststep_base":(C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, C.c_int, C.c_int, C.c_int, _f64, _vp, _vp]),
     "bmf_faststep_eval_work": (_i64, [_i64, _i64, _i32, _i32]),
     "bmf_faststep_eval": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bmf_concept_scan_work": (_i64, [_i32]),

@@ -4,6 +4,10 @@ search on the sigmoid-smoothed reconstruction error.  Drop-in for ``PyBMF/models
 F(u, v) and its gradient are each ONE tile-fused pass on the GPU (csrc/residual.hip, ``bmf_thresh_eval``): the m x n
 product of the sigmoid-transformed factors is never materialised.  The line search (``solvers/line_search.py``) and the
 outer loop (:82-147) are host control flow, as in the reference.
+
+A rank 64 < k <= 128 (Boolean X, one GPU) keeps the factors as 128 fp64 columns and evaluates the objective with the kernels of
+csrc/thresh_wide.hip: the trace form under the all-ones mask, the pass over the observed cells under W = 'mask' / weights; the
+tile-product objective stays at k <= 64.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ class BinaryMFThreshold(ContinuousModel):
         assert ismat(self.W) or self.W in ['mask', 'full']
 
     def fit(self, X_train, X_val=None, X_test=None, **kwargs):
+        self._check_wide_rank(X_train)
         super().fit(X_train, X_val, X_test, **kwargs)
         self._fit()
         self.X_pd = None  # Boolean product at the learnt (u, v), built on first access
@@ -90,11 +95,32 @@ class BinaryMFThreshold(ContinuousModel):
         self.X_pd = None
         self.evaluate(df_name='updates', head_info={'iter': n_iter, 'u': self.u, 'v': self.v, 'F': new_fval})
 
+    # ---- rank 64 < k <= 128 (csrc/thresh_wide.hip) -------------------------------------------------------------
+    def _wide(self):
+        from .. import _lib as L
+        return self.k > L.MAX_KP
+
+    def _check_wide_rank(self, X_train=None):
+        """What a rank above 64 does not take, refused before anything is uploaded: k > 128 and data that is not 0 / 1 (the cell-list
+        objective of real-valued data is built for k <= 64 only)."""
+        if not self._wide():
+            return
+        from ..wide import MAX_K_WIDE
+        if self.k > MAX_K_WIDE:
+            raise NotImplementedError(f"k={self.k}: this build supports k <= {MAX_K_WIDE}")
+        if not (self._boolean if X_train is None else self._values_are_boolean(X_train)):   # (X_train None: after the upload, which decides)
+            raise NotImplementedError(f"k={self.k}: BinaryMFThreshold at a rank above 64 takes Boolean (0/1) data; real-valued data needs k <= 64")
+
     # ---- device side ------------------------------------------------------------------------------------------
     def _upload_factors(self):
         import torch
         B = self._bits
-        self._kp = 32 if self.k <= 32 else 64
+        wide = self._wide()
+        if wide:
+            self._check_wide_rank()
+            if getattr(self, "_sharded", False) or getattr(self, "_rows", (0, self.m)) != (0, self.m):
+                raise NotImplementedError(f"k={self.k}: a rank above 64 runs on one GPU (a sharded run needs k <= 64)")
+        self._kp = 128 if wide else (32 if self.k <= 32 else 64)
         dev = B.device
         # fp64 on the device: the line search compares F values that differ by min_diff = 1e-3 on F ~ 1e4 (csrc/thresh64.hip)
         from .._lib import lib
@@ -103,7 +129,8 @@ class BinaryMFThreshold(ContinuousModel):
         self._Ud[: self.m, : self.k] = torch.from_numpy(np.ascontiguousarray(self.U, dtype=np.float64)).to(dev)
         self._Vd[: self.n, : self.k] = torch.from_numpy(np.ascontiguousarray(self.V, dtype=np.float64)).to(dev)
         self._mblocks = 1024
-        n_work = int(lib.bmf_thresh_eval64_work(B.m_pad, B.n_pad, self._kp))
+        # (a wide rank has no tile-product objective: its workspace is the transformed factors of the cell-list form alone)
+        n_work = 0 if wide else int(lib.bmf_thresh_eval64_work(B.m_pad, B.n_pad, self._kp))
         self._work = torch.zeros((max(n_work, (2 * B.m_pad + 2 * B.n_pad) * self._kp + 4 * self._mblocks),), dtype=torch.float64, device=dev)
         self._out = torch.zeros(4, dtype=torch.float64, device=dev)
         # stream handle and device index looked up once per fit: an evaluation is ~50 us of kernels, torch's current_stream() /
@@ -128,6 +155,9 @@ class BinaryMFThreshold(ContinuousModel):
         self._poll = True   # wait for the result words in pinned memory (bounded) instead of a stream synchronisation: -15 us per evaluation
         self._F_memo, self._dF_memo = {}, {}
         self._setup_trace()
+        if wide and self._trace is None and getattr(self, "_obs", None) is None:
+            raise NotImplementedError(f"k={self.k}: the tile-product objective (BMF_THRESH_TRACE=0, or a list of ones / a workspace that does "
+                                      "not fit the memory budget) is built for k <= 64; a rank above 64 has the trace form only")
         # Stream contract of the dense evaluation: every launch of this fit goes to the stream that was current HERE and each
         # evaluation synchronises that stream before it returns its numbers, so the results do not depend on what the caller's
         # current stream is at evaluation time; the factors above were uploaded from pageable host memory (synchronous copies),
@@ -175,17 +205,19 @@ class BinaryMFThreshold(ContinuousModel):
             nseg = int(seg_row.numel())
             if idx.numel() == 0 or nseg == 0 or nseg > 8 * self.m + 64:
                 return
-            max_pairs = int(lib.bmf_thresh_trace64_max_pairs(self.k))
+            trace_max_pairs, trace_work = ((lib.bmf_thresh_trace_wide_max_pairs, lib.bmf_thresh_trace_wide_work) if self._wide() else
+                                           (lib.bmf_thresh_trace64_max_pairs, lib.bmf_thresh_trace64_work))
+            max_pairs = int(trace_max_pairs(self.k))
             # The workspace grows with the pairs evaluated per call (~ 2 pairs (m + n + 2) k doubles + Grams + cell partials: 1.6 GB at
             # 100k x 100k, k = 32, 32 pairs).  Keep it within a budget -- a quarter of the free device memory, at most 2 GiB -- by
             # evaluating fewer pairs per call; when even one pair does not fit, the tile-product objective (its workspace is 2 (m + n) k
             # doubles) takes the fit instead of an out-of-memory error.  (advisor, round 4)
             free_b, _ = torch.cuda.mem_get_info(dev)
             budget = min(free_b // 4, 2 << 30)
-            n_work = int(lib.bmf_thresh_trace64_work(self.m, self.n, self.k, max_pairs))
+            n_work = int(trace_work(self.m, self.n, self.k, max_pairs))
             while max_pairs > 1 and n_work * 8 > budget:
                 max_pairs //= 2
-                n_work = int(lib.bmf_thresh_trace64_work(self.m, self.n, self.k, max_pairs))
+                n_work = int(trace_work(self.m, self.n, self.k, max_pairs))
             if n_work <= 0 or n_work * 8 > budget:
                 return
             try:
@@ -200,15 +232,16 @@ class BinaryMFThreshold(ContinuousModel):
         """F (and dF) at every point of `points` in one enqueue; fills the memo tables."""
         from .._lib import lib, check, ptr
         tr = self._trace
+        entry, name = (lib.bmf_thresh_trace_wide, "bmf_thresh_trace_wide") if self._kp == 128 else (lib.bmf_thresh_trace64, "bmf_thresh_trace64")
         pts = [(float(p_[0]), float(p_[1])) for p_ in points]
         for a in range(0, len(pts), tr["max_pairs"]):
             part = pts[a:a + tr["max_pairs"]]
             uv = (C.c_double * (2 * len(part)))(*[x for pr in part for x in pr])
             tr["seq"] += 1.0
             seq, out = tr["seq"], tr["out"]
-            check(lib.bmf_thresh_trace64(ptr(tr["seg_row"]), ptr(tr["seg_beg"]), ptr(tr["seg_len"]), tr["nseg"], ptr(tr["idx"]), self.m, self.n, ptr(self._Ud), ptr(self._Vd), self._kp, self.k, uv,
-                                         len(part), float(self.lamda), tr["sum_x"], int(want_grad), ptr(tr["work"]), ptr(tr["out_host"]),
-                                         seq, self._stream_ptr), "bmf_thresh_trace64")
+            check(entry(ptr(tr["seg_row"]), ptr(tr["seg_beg"]), ptr(tr["seg_len"]), tr["nseg"], ptr(tr["idx"]), self.m, self.n, ptr(self._Ud), ptr(self._Vd), self._kp, self.k, uv,
+                        len(part), float(self.lamda), tr["sum_x"], int(want_grad), ptr(tr["work"]), ptr(tr["out_host"]),
+                        seq, self._stream_ptr), name)
             # every pair's word 0 and the word after the last pair carry this call's sequence number, each written behind the results it
             # vouches for: wait for ALL of them (bounded), else for the stream.  (Waiting for the last word alone relied on writes to
             # host memory from different blocks becoming visible in fence order; once in ~10^5 calls a slot still held the previous
@@ -294,19 +327,31 @@ class BinaryMFThreshold(ContinuousModel):
             Us, dUs, Vs, dVs, part = (self._work[0:mp], self._work[mp:2 * mp], self._work[2 * mp:2 * mp + np_],
                                       self._work[2 * mp + np_:2 * mp + 2 * np_], self._work[2 * mp + 2 * np_:])
             s = _stream()
-            check(lib.bmf_thresh_transform64(ptr(self._Ud), B.m_pad, self.m, self.k, kp, u, float(self.lamda), ptr(Us),
-                                             ptr(dUs) if want_grad else None, s), "bmf_thresh_transform64")
-            check(lib.bmf_thresh_transform64(ptr(self._Vd), B.n_pad, self.n, self.k, kp, v, float(self.lamda), ptr(Vs),
-                                             ptr(dVs) if want_grad else None, s), "bmf_thresh_transform64")
+            if kp == 128:
+                check(lib.bmf_thresh_transform64_wide(ptr(self._Ud), B.m_pad, self.m, self.k, u, float(self.lamda), ptr(Us),
+                                                      ptr(dUs) if want_grad else None, s), "bmf_thresh_transform64_wide")
+                check(lib.bmf_thresh_transform64_wide(ptr(self._Vd), B.n_pad, self.n, self.k, v, float(self.lamda), ptr(Vs),
+                                                      ptr(dVs) if want_grad else None, s), "bmf_thresh_transform64_wide")
+            else:
+                check(lib.bmf_thresh_transform64(ptr(self._Ud), B.m_pad, self.m, self.k, kp, u, float(self.lamda), ptr(Us),
+                                                 ptr(dUs) if want_grad else None, s), "bmf_thresh_transform64")
+                check(lib.bmf_thresh_transform64(ptr(self._Vd), B.n_pad, self.n, self.k, kp, v, float(self.lamda), ptr(Vs),
+                                                 ptr(dVs) if want_grad else None, s), "bmf_thresh_transform64")
             # the three sums land in words 1..3 of the pinned result array (word 0 is unused here), written -- not accumulated -- by the
             # last launch; the host waits for those words, as in the dense evaluation
             out = self._out_np
             out[0] = 0.0
             pending = self._mark_pending(slice(1, 4))
-            check(lib.bmf_masked_thresh64_k(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), ptr(ls["wgt"]), ptr(ls["seg_row"]),
-                                            ptr(ls["seg_beg"]), ls["nseg"], ptr(Us), ptr(dUs) if want_grad else None, ptr(Vs),
-                                            ptr(dVs) if want_grad else None, kp, self.k, ptr(part), self._mblocks,
-                                            C.c_void_p(self._out_host.data_ptr() + 8), s), "bmf_masked_thresh64_k")
+            if kp == 128:
+                check(lib.bmf_masked_thresh64_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), ptr(ls["wgt"]), ptr(ls["seg_row"]),
+                                                   ptr(ls["seg_beg"]), ls["nseg"], ptr(Us), ptr(dUs) if want_grad else None, ptr(Vs),
+                                                   ptr(dVs) if want_grad else None, self.k, ptr(part), self._mblocks,
+                                                   C.c_void_p(self._out_host.data_ptr() + 8), s), "bmf_masked_thresh64_wide")
+            else:
+                check(lib.bmf_masked_thresh64_k(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), ptr(ls["wgt"]), ptr(ls["seg_row"]),
+                                                ptr(ls["seg_beg"]), ls["nseg"], ptr(Us), ptr(dUs) if want_grad else None, ptr(Vs),
+                                                ptr(dVs) if want_grad else None, kp, self.k, ptr(part), self._mblocks,
+                                                C.c_void_p(self._out_host.data_ptr() + 8), s), "bmf_masked_thresh64_k")
             launch_stream = torch.cuda.current_stream()   # the stream the launches above went to (_stream())
             if self._poll:
                 self._wait_words(pending, slice(1, 4), launch_stream)
