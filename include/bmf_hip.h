@@ -517,8 +517,34 @@ typedef struct {
                                              local TP, FP when ubits_prev / vbits_prev are set, spare otherwise */
     double* log;                          /* [log_rows][BMF_LOG_COLS] */
     int32_t log_rows; int32_t _pad3;
-    int32_t* stop;                        /* device flag: 0 running, else the iteration that tripped early stop */
-    double sum_x;                         /* sum(X) over ALL ranks */
+    int32_t* stop;                        /* device flag: 0 running, else the iteration that tripped early stop.  Iterations are enqueued
+                                             blindly behind it; what their launches leave (pinned by tests/test_driver_gpu.py):
+                                             FROZEN, byte for byte as the stopping iteration left them: U64, V64, U, V, ubits, vbits,
+                                               ucolbits, vcolbits, ubits_prev, vbits_prev, counts, Upanel, Vpanel, scaleU, scaleV, GU, GV,
+                                               scal, log (no row past the stop) and stop itself.
+                                             SET TO A STATED VALUE: comm[0..8) -- kept by bmf_penalty_run (its gather rides in the
+                                               finalize launch, which returns at once), zeroed by the gather launch of
+                                               bmf_penalty_update[_head] (a row-sharded run keeps all-reducing the block until the host
+                                               notices: zeros stay zeros).  GV64 and comm[8..) -- zeroed by the fused plane rebuild with
+                                               BMF_PANEL_I8, rewritten to the same bytes from the unchanged factor with the other panels.
+                                               Nred -- a block of nred_blocks == 2 is zeroed by bmf_penalty_update_xtu(block); the
+                                               unblocked Nred is rewritten to the same bytes from the unchanged slabs by
+                                               bmf_penalty_update and bmf_penalty_update_xtu(-1).
+                                             SCRATCH, unspecified: Mslab (summed in place again at splits_xv >= 6), Nslab, gram_slabs,
+                                               panel_ws, partU, partV, mae_ws -- and Nred behind bmf_penalty_run at n_pad * kp >= 65536,
+                                               where the slab sum shares a launch with the log row and races with the flag raised beside
+                                               it: an element holds the stopping iteration's sum or the one before.  Nred is only read by
+                                               a V update that the flag cancels.
+                                             bmf_penalty_finalize(iter) behind a flag s: iter > s writes nothing; iter <= s is the call
+                                             that wrote row s, repeated -- row, GU and scal[1] are written again, the rule is evaluated
+                                             again and the flag moves only if it trips (to iter); it is never cleared.
+                                             Before the stop, bmf_penalty_run, _update_head + _update_xtu(-1) + _finalize and _update +
+                                             _finalize leave the same bytes in all of the above but the scratch -- with one exception:
+                                             without mae_ws the MAE pass is bmf_residual_sums, whose workgroups add into comm[4], comm[5]
+                                             with fp64 atomics in the order they finish; those two and LOG_MAE then agree between two
+                                             runs to 2 (B + 1) 2^-53 relatively, B = the workgroups of bmf_residual_plan.  Nothing else
+                                             reads them. */
+    double sum_x;                        /* sum(X) over ALL ranks */
     double cells;                         /* m_total * n */
     double tol, min_diff;                 /* early-stop parameters (models/BaseModelTools.py:326-334) */
     float thr_u, thr_v;                   /* 0.5 / 0.5 for BinaryMFPenalty */
