@@ -69,7 +69,7 @@ const char* bmf_last_error(void);
 /* sizeof() of the argument structs as THIS library was compiled, so that a binding can refuse a mismatch before the first call
  * (the structs that are passed without a struct_bytes field of their own included): which = 0 bmf_epilogue_args, 1 bmf_palm_args,
  * 2 bmf_penalty_state, 3 bmf_wnmf_real_state, 4 bmf_palm_state, 5 bmf_masked_loop, 6 bmf_masked_side, 7 bmf_link_loop,
- * 8 bmf_nmf_state; -1 for an unknown id. */
+ * 8 bmf_nmf_state, 9 bmf_palm_wide_args; -1 for an unknown id. */
 int bmf_struct_bytes(int which);
 
 /* position of local reduction index cl (0..127) inside its 128-block of a factor panel (host helper) */
@@ -1338,6 +1338,41 @@ int bmf_cover_count_wide(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, i
  * copy with x_tiled = 1.  ws: (m_pad + n_pad) * 128 uint16.  m_pad % 256 == 0, n_pad % 64 == 0. */
 int bmf_resid_sums_wide(const uint32_t* XTbits, int64_t ldxt, int64_t m_pad, int64_t n_pad, const float* UA, const float* UB,
                         const float* VA, const float* VB, uint16_t* ws, double* sums, int x_tiled, void* stream);
+
+/* ---- the proximal step at a rank 64 < k <= 128 (csrc/palm_wide.hip) ----------------------------------------------------------------
+ * bmf_sym_norms for the Gram of a wide factor: G64 is the symmetric positive semi-definite 128 x 128 fp64 matrix, row-major,
+ * assembled from the four 64 x 64 block Grams (zero rows and columns beyond k); out[0] = spectral norm, out[1] = Frobenius norm.  One
+ * workgroup with one copy of the matrix in LDS (the squared iterate is held in registers and written over it); every sum in a fixed
+ * order; the zero matrix gives out[0] = 0. */
+int bmf_sym_norms_wide(const double* G64, double* out, void* stream);
+
+typedef struct {
+    int32_t struct_bytes;  /* sizeof(bmf_palm_wide_args), checked */
+    int32_t rows, k;       /* 64 < k <= 128: block 0 holds 64 real columns, block 1 holds k - 64 */
+    int32_t splits;
+    int64_t rows_pad;      /* multiple of 128 */
+    int64_t slab_stride;   /* >= rows_pad * 64 */
+    double* F64[2];        /* per block: rows_pad x 64 fp64 master, updated in place */
+    double* Fprev64[2];    /* per block: the point the inertial term extrapolates from; see advance_prev */
+    float* F[2];           /* out, per block: fp32 shadow of the new factor */
+    const float* num[2];   /* per block: X G_b from bmf_xf_bits_i8, [splits][rows_pad][64] slabs */
+    const float* G[2][2];  /* G[a][b]: 64 x 64 fp32 block (rows of block a, columns of block b) of the OTHER factor's 128 x 128 Gram */
+    const double* norms;   /* bmf_sym_norms_wide output for that Gram */
+    int32_t norm_kind;     /* BMF_NORM_* */
+    int32_t variant;       /* BMF_PALM_* */
+    double beta, l1, l2, gap_l1, gap_l2;   /* as in bmf_palm_args */
+    int32_t advance_prev;
+    float thr;
+    uint64_t* rowbits[2];  /* out, per block: one 64-bit word of thresholded bits per row */
+    uint32_t* colbits[2];  /* out, per block: [64][ldcb] bit-columns */
+    int64_t ldcb;
+    double* partials[2];   /* out, per block: [rows_pad / 128] integrality gap per 128-row block */
+} bmf_palm_wide_args;
+/* bmf_palm_epilogue under the all-ones mask over both blocks of a wide factor: Fe = F + beta (F - Fprev), grad = Fe G - num with the
+ * reduction over all 128 columns, then the same fp64 element-wise step, shadows, bits and gap partials per block.  Columns >= k and
+ * rows >= rows are written as exact zeros.  (A mask / weight matrix needs no kernel of its own: bmf_masked_pass_wide gives num and den
+ * per block and bmf_palm_epilogue runs once per block with `den` set and `norms` from bmf_sym_norms_wide.) */
+int bmf_palm_epilogue_wide(const bmf_palm_wide_args* args, void* stream);
 
 /* ---- kernel timing (bench.py roofline leg) ----------------------------------------------------------------------- */
 

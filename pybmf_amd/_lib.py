@@ -84,6 +84,16 @@ class PalmArgs(C.Structure):
     ]
 
 
+class PalmWideArgs(C.Structure):
+    """bmf_palm_wide_args"""
+    _fields_ = [
+        ("struct_bytes", _i32), ("rows", _i32), ("k", _i32), ("splits", _i32), ("rows_pad", _i64), ("slab_stride", _i64),
+        ("F64", _vp * 2), ("Fprev64", _vp * 2), ("F", _vp * 2), ("num", _vp * 2), ("G", (_vp * 2) * 2), ("norms", _vp),
+        ("norm_kind", _i32), ("variant", _i32), ("beta", _f64), ("l1", _f64), ("l2", _f64), ("gap_l1", _f64), ("gap_l2", _f64),
+        ("advance_prev", _i32), ("thr", _f32), ("rowbits", _vp * 2), ("colbits", _vp * 2), ("ldcb", _i64), ("partials", _vp * 2),
+    ]
+
+
 class PalmState(C.Structure):
     """bmf_palm_state"""
     _fields_ = [
@@ -320,6 +330,8 @@ SIGNATURES = {
     "bmf_gram_cross": (C.c_int, [_vp, _vp, _i64, _vp, C.c_int, _vp]),
     "bmf_cover_count_wide": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "bmf_resid_sums_wide": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "bmf_sym_norms_wide": (C.c_int, [_vp, _vp, _vp]),
+    "bmf_palm_epilogue_wide": (C.c_int, [C.POINTER(PalmWideArgs), _vp]),
     "bmf_masked_scalars": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "bmf_palm_scalars": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "bmf_palm_iterate": (C.c_int, [_vp, C.c_int, _f64, _f64, _f64, _f64, C.c_int, _vp]),
@@ -355,7 +367,7 @@ def _load():
     # the ctypes mirrors against the library's own sizeof(): a header / binding mismatch fails here, not as a corrupted launch
     if lib.bmf_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.bmf_version()}, this binding was written for {ABI_VERSION} (rebuild the library)")
-    for which, mirror in enumerate((EpilogueArgs, PalmArgs, PenaltyState, WnmfRealState, PalmState, MaskedLoop, MaskedSide, LinkLoop, NmfState)):
+    for which, mirror in enumerate((EpilogueArgs, PalmArgs, PenaltyState, WnmfRealState, PalmState, MaskedLoop, MaskedSide, LinkLoop, NmfState, PalmWideArgs)):
         if lib.bmf_struct_bytes(which) != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: sizeof({mirror.__doc__}) is {lib.bmf_struct_bytes(which)} in the library, {C.sizeof(mirror)} in the binding")
     return lib

@@ -28,6 +28,7 @@ extern "C" int bmf_struct_bytes(int which) {
         case 6: return (int)sizeof(bmf_masked_side);
         case 7: return (int)sizeof(bmf_link_loop);
         case 8: return (int)sizeof(bmf_nmf_state);
+        case 9: return (int)sizeof(bmf_palm_wide_args);
         default: return -1;
     }
 }

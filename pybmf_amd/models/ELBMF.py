@@ -51,11 +51,12 @@ class ELBMF(ContinuousModel):
         self.iPALM()
 
     def iPALM(self):
-        from ..palm import PalmEngine
+        from ..palm_wide import palm_engine
         if getattr(self, "task", None) is None:
             raise AttributeError(f"'{type(self).__name__}' object has no attribute 'task'")
         obs = getattr(self, "_obs", None)
-        eng = self._eng = PalmEngine(self._bits, self.k, L.PALM_ELBMF, beta=float(self.beta), obs=obs)
+        # (k <= 64: palm.PalmEngine; 64 < k <= 128: the two-block palm_wide.WidePalmEngine, stepwise loop below)
+        eng = self._eng = palm_engine(self._bits, self.k, L.PALM_ELBMF, beta=float(self.beta), obs=obs, sharded=self._sharded)
         eng.load_factors(self.U, self.V)
         rows, self.counts = [], []
         state = {"gap": np.inf}
@@ -146,7 +147,7 @@ def prox(U, kai, lamda):
 def update_U(X, U, V, W, reg_l1, reg_l2, beta, U_last, device="cuda:0"):
     """One Gauss-Seidel step for U on the GPU (ELBMF.py:177-196); call it with X.T, V, U for V.  Returns (U_new, U)."""
     from ..engine import BitMatrix
-    from ..palm import PalmEngine
+    from ..palm_wide import palm_engine
     from .BinaryMFPenalty import _is_full
     from .ContinuousModel import ContinuousModel
     ContinuousModel._check_boolean(X)   # anything but 0 / 1 is refused, never silently binarised
@@ -161,7 +162,7 @@ def update_U(X, U, V, W, reg_l1, reg_l2, beta, U_last, device="cuda:0"):
             raise ValueError("W must have the shape of X")
         Xd = np.asarray(X.todense()) if hasattr(X, "todense") else np.asarray(X)
         obs = SparseObs(Wc.row, Wc.col, np.asarray(Xd[Wc.row, Wc.col], dtype=np.float64).ravel(), Wc.data, X.shape, device)
-    eng = PalmEngine(BitMatrix(X, device), U.shape[1], L.PALM_ELBMF, beta=float(beta), obs=obs)
+    eng = palm_engine(BitMatrix(X, device), U.shape[1], L.PALM_ELBMF, beta=float(beta), obs=obs)
     eng.load_factors(U, V, U_prev=np.asarray(U_last, dtype=np.float64))
     eng.step("U", reg_l1, reg_l2)
     return eng.factors()[0], U

@@ -127,9 +127,9 @@ def elbmf_step_ipalm(X, U, V, Uold, l1reg, l2reg, tau, beta, device="cuda:0"):
     """One inertial proximal step of U on the GPU (PRIMP.py:71-88): ``V`` is k x n, ``Uold`` the anchor of the inertial term
     (ignored when beta == 0); call it with ``X.T, V.T, U.T, Vold`` for the other factor, as the reference's loop does.  Returns the
     new U; unlike the reference it does not also modify the ``U`` it was given in place."""
-    from ..palm import PalmEngine
+    from ..palm_wide import palm_engine
     Un, Vn = _np64(U), np.ascontiguousarray(_np64(V).T)
-    eng = PalmEngine(_bits_of(X, device), Un.shape[1], L.PALM_PRIMP, beta=float(beta))
+    eng = palm_engine(_bits_of(X, device), Un.shape[1], L.PALM_PRIMP, beta=float(beta))
     eng.load_factors(Un, Vn, U_prev=None if (Uold is None or beta == 0) else _np64(Uold))
     eng.step("U", float(l1reg), float(l2reg) * float(tau), advance_prev=False)
     return _like(eng.factors()[0], U)
@@ -167,9 +167,9 @@ def primp(X, n_components, l1reg=0.01, l2reg=0, regularization_rate=lambda t: 1.
 def _ipalm_run(bits, U, V, l1reg, l2reg, regularization_rate, maxiter, tolerance, beta, callback=None):
     """The loop itself.  ``bits``: engine.BitMatrix; ``V`` is n x k here; ``callback(t, U, V[n x k], fn)``.  Returns (U, V, [||X - U
     V^T||_F^2 per iteration])."""
-    from ..palm import PalmEngine
+    from ..palm_wide import palm_engine
     U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-    eng = PalmEngine(bits, U.shape[1], L.PALM_PRIMP, beta=float(beta))
+    eng = palm_engine(bits, U.shape[1], L.PALM_PRIMP, beta=float(beta))   # (64 < k <= 128: the two-block engine, stepwise loop below)
     eng.load_factors(U, V)            # the anchors of the inertial term stay the initial factors (advance_prev=False below)
     fn, fns = np.inf, []
     maxiter = int(maxiter)
