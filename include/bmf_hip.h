@@ -1374,6 +1374,31 @@ typedef struct {
  * per block and bmf_palm_epilogue runs once per block with `den` set and `norms` from bmf_sym_norms_wide.) */
 int bmf_palm_epilogue_wide(const bmf_palm_wide_args* args, void* stream);
 
+/* ---- the link passes at a rank 64 < k <= 128 (csrc/link_wide.hip) --------------------------------------------------------------------
+ * PNLPF and WNMF with the Kullback-Leibler loss.  The link is applied to the dot product over ALL 128 columns, so the product cannot be
+ * formed per 64-column block: these passes form P over both blocks, send it through the link and contract into both output blocks.
+ * Factors in the layout of pybmf_amd/wide.py: fp32, [rows_pad][64] per block, zero padded (block 1 holds k - 64 real columns).
+ *
+ * bmf_link_pass_wide = bmf_link_pass for such a factor: num0 / num1 (and den0 / den1, sigmoid link) are [splits][rows_pad][64] slab
+ * arrays (stride slab_stride >= rows_pad * 64), to be summed in slab order; splits = bmf_link_splits(rows, cols).  Exact-fp32 MFMA, the
+ * sigmoid link with its 64 MFMA steps added in fp64.  The padding contract of bmf_link_pass holds: every cell is masked by rows / cols
+ * (bits of X beyond them are ignored), factor padding must be zero, output rows >= rows are written as exact zeros.  KL: den* are not
+ * written and may be NULL.  k <= 64 (bmf_link_pass) and k > 128 are refused. */
+int bmf_link_pass_wide(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, int32_t rows, int32_t cols, const float* Fself0,
+                       const float* Fself1, const float* Fother0, const float* Fother1, int64_t other_pad, int k, int link, double lamda,
+                       float* num0, float* num1, float* den0, float* den1, int64_t slab_stride, int splits, void* stream);
+/* bmf_link_sums with P over both blocks: the same three sums, the same optional Obits. */
+int bmf_link_sums_wide(const uint32_t* Xbits, int64_t m_pad, int64_t ldx, int32_t m, int32_t n, const float* U0, const float* U1,
+                       const float* V0, const float* V1, int64_t n_pad, int k, int link, double lamda, const uint32_t* Obits, double* sums,
+                       void* stream);
+/* bmf_masked_pass_wide with the link / lamda arguments of bmf_masked_link_pass: p_e is the dot product over both blocks, the sigmoid or
+ * the reciprocal is applied per cell, numerators and denominators come out per block (KL: den* are zero, the caller supplies the column
+ * sums), `sums` as in bmf_masked_link_pass.  link = 0 is refused: that is bmf_masked_pass_wide. */
+int bmf_masked_link_pass_wide(const int64_t* ptr, const int32_t* idx, const float* val, const float* wgt, int32_t rows,
+                              const int32_t* seg_row, const int64_t* seg_beg, int32_t nseg, const int64_t* row_seg_ptr, const float* Fself0,
+                              const float* Fself1, const float* Fother0, const float* Fother1, float* part0, float* part1, float* num0,
+                              float* num1, float* den0, float* den1, double* sums, int link, double lamda, void* stream);
+
 /* ---- kernel timing (bench.py roofline leg) ----------------------------------------------------------------------- */
 
 /* When enabled, bmf_xf_bits launches made through bmf_penalty_update (and the two sweep launches of bmf_nmf_cd_iterate) are bracketed by hipEvents on `stream`

@@ -332,6 +332,10 @@ SIGNATURES = {
     "bmf_resid_sums_wide": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "bmf_sym_norms_wide": (C.c_int, [_vp, _vp, _vp]),
     "bmf_palm_epilogue_wide": (C.c_int, [C.POINTER(PalmWideArgs), _vp]),
+    "bmf_link_pass_wide": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _f64, _vp, _vp, _vp, _vp, _i64,
+                                     C.c_int, _vp]),
+    "bmf_link_sums_wide": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _f64, _vp, _vp, _vp]),
+    "bmf_masked_link_pass_wide": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp] + [_vp] * 11 + [C.c_int, _f64, _vp]),
     "bmf_masked_scalars": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "bmf_palm_scalars": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "bmf_palm_iterate": (C.c_int, [_vp, C.c_int, _f64, _f64, _f64, _f64, C.c_int, _vp]),

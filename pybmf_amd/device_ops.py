@@ -235,21 +235,34 @@ class MaskedOneStep:
         vals = np.asarray(Xs[Wc.row, Wc.col]).ravel()
         obs = SparseObs(Wc.row, Wc.col, vals, Wc.data, X.shape, device)
         bits = BitMatrix(X, device) if link else None   # (the link engine scores against the Boolean X)
-        self.eng = MaskedMUEngine(obs, U.shape[1], mode, bits=bits, link=link, lamda=lamda)
+        self.wide = bool(link) and U.shape[1] > L.MAX_KP   # a link model at a rank 64 < k <= 128: two 64-column blocks per factor
+        if self.wide:
+            from .link_wide import link_engine
+            self.eng = link_engine(bits, U.shape[1], link, mode, lamda=lamda, obs=obs)
+        else:
+            self.eng = MaskedMUEngine(obs, U.shape[1], mode, bits=bits, link=link, lamda=lamda)
         self.eng.load_factors(U, V)
+
+    def _epilogue(self, which, reg):
+        e = self.eng
+        if self.wide:
+            for b in range(2):
+                e._epilogue(which, b, e.mode, float(reg))
+        else:
+            e._epilogue(which, e.mode, float(reg))
 
     def update_U(self, reg):
         e = self.eng
         with torch.cuda.device(e.device):
             e._pass(e.obs.csr, e.m, e.U, e.V, e.numU, e.denU, None)
-            e._epilogue("U", e.mode, float(reg))
+            self._epilogue("U", reg)
         return e.factors()[0]
 
     def update_V(self, reg):
         e = self.eng
         with torch.cuda.device(e.device):
             e._pass(e.obs.csc, e.n, e.V, e.U, e.numV, e.denV, None)
-            e._epilogue("V", e.mode, float(reg))
+            self._epilogue("V", reg)
         return e.factors()[1]
 
     def errors(self, reg):

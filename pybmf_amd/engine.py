@@ -1018,17 +1018,21 @@ class ObservedScorer:
             return float("nan"), float("nan")
         ls = self.obs.csr
         if isinstance(U, (list, tuple)):   # 64 < k <= 128: two blocks of 64 columns per factor (pybmf_amd/wide.py)
-            if link:
-                raise NotImplementedError("scores against a link prediction take k <= 64")
             with torch.cuda.device(self.device):
                 if "wide" not in self._scratch:
                     z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)  # noqa: E731
                     self._scratch["wide"] = [z(self.m, 64) for _ in range(4)] + [z(max(ls["nseg"], 1), 2, 64) for _ in range(2)]
                 n0, n1, d0, d1, p0, p1 = self._scratch["wide"]
                 self.sums.zero_()
-                check(lib.bmf_masked_pass_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), None, self.m, ptr(ls["seg_row"]), ptr(ls["seg_beg"]),
-                                               ls["nseg"], ptr(ls["row_seg_ptr"]), ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]), ptr(p0), ptr(p1),
-                                               ptr(n0), ptr(n1), ptr(d0), ptr(d1), ptr(self.sums), _stream()), "bmf_masked_pass_wide")
+                if link:   # the sums of the pass are taken against the link prediction (bmf_masked_link_pass_wide)
+                    check(lib.bmf_masked_link_pass_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), None, self.m, ptr(ls["seg_row"]),
+                                                        ptr(ls["seg_beg"]), ls["nseg"], ptr(ls["row_seg_ptr"]), ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]),
+                                                        ptr(p0), ptr(p1), ptr(n0), ptr(n1), ptr(d0), ptr(d1), ptr(self.sums), int(link), float(lamda),
+                                                        _stream()), "bmf_masked_link_pass_wide")
+                else:
+                    check(lib.bmf_masked_pass_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), None, self.m, ptr(ls["seg_row"]), ptr(ls["seg_beg"]),
+                                                   ls["nseg"], ptr(ls["row_seg_ptr"]), ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]), ptr(p0), ptr(p1),
+                                                   ptr(n0), ptr(n1), ptr(d0), ptr(d1), ptr(self.sums), _stream()), "bmf_masked_pass_wide")
                 s = self.sums.cpu().numpy()
             return float(np.sqrt(s[0] / self.nnz)), float(s[1] / self.nnz)
         with torch.cuda.device(self.device):
@@ -1089,9 +1093,16 @@ class WholeScorer:
     def real(self, U, V, kp, link=None, lamda=0.0):
         cells = float(self.m) * float(self.n)
         if isinstance(U, (list, tuple)):   # 64 < k <= 128: the residual sums with the product over both blocks (bmf_resid_sums_wide)
-            if link or self.bits is None:
-                raise NotImplementedError("a rank above 64 scores Boolean (0/1) data sets against U V^T only")
+            if self.bits is None:
+                raise NotImplementedError("a rank above 64 scores Boolean (0/1) data sets only")
             B = self.bits
+            if link:   # against the link prediction over both blocks (every one of the 128 columns: the padding is zero)
+                with torch.cuda.device(self.device):
+                    self.sums.zero_()
+                    check(lib.bmf_link_sums_wide(ptr(B.bits), B.m_pad, B.ldx, self.m, self.n, ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]), B.n_pad, 128,
+                                                 int(link), float(lamda), None, ptr(self.sums), _stream()), "bmf_link_sums_wide")
+                    s = self.sums.cpu().numpy()
+                return float(np.sqrt(s[1] / cells)), float(s[0] / cells)
             with torch.cuda.device(self.device):
                 if getattr(self, "_wide_ws", None) is None:
                     self._wide_ws = torch.zeros(((B.m_pad + B.n_pad) * 2 * 64,), dtype=torch.int16, device=self.device)

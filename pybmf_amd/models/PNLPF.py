@@ -7,7 +7,8 @@ Drop-in for ``PyBMF.models.PNLPF`` (``PyBMF/models/PNLPF.py``):
 The loop is the inherited ``BinaryMFPenalty._fit_masked`` (BinaryMFPenalty.py:61-115); the two updates (:61-91) cannot be
 re-associated, so each is one tile-fused pass over X (csrc/link.hip, ``bmf_link_pass``) followed by the shared fp64
 epilogue.  Under a mask / weight matrix the contractions run over the observed cells instead (csrc/masked.hip,
-``bmf_masked_link_pass``).
+``bmf_masked_link_pass``).  A rank 64 < k <= 128 runs on the same passes over two 64-column blocks per factor (csrc/link_wide.hip,
+pybmf_amd/link_wide.py).
 """
 from __future__ import annotations
 
@@ -26,6 +27,10 @@ class PNLPF(BinaryMFPenalty):
 
     def _link_engine(self):
         from ..engine import LinkMUEngine, MaskedMUEngine
+        if self.k > L.MAX_KP:   # two 64-column blocks per factor: the link passes over both blocks (pybmf_amd/link_wide.py)
+            from ..link_wide import link_engine
+            return link_engine(self._bits if self._boolean else None, self.k, L.LINK_SIGMOID, L.MODE_PENALTY, lamda=float(self.link_lamda),
+                               obs=getattr(self, "_obs", None), sharded=self._sharded, boolean=self._boolean)
         if getattr(self, "_obs", None) is not None:
             # W = 'mask' on a csr with unstored cells, or a weight matrix: both contractions of an update run over the observed cells
             # (multiply(W, multiply(X, d_sig)) @ V and multiply(W, multiply(sig, d_sig)) @ V, PNLPF.py:65-68,81-84), rec_error over
@@ -79,7 +84,12 @@ def _one_step(X, W, U, V, reg, link_lamda, which):
         from ..device_ops import MaskedOneStep
         step = MaskedOneStep(X, W, U, V, mode=L.MODE_PENALTY, link=L.LINK_SIGMOID, lamda=float(link_lamda))
         return step.update_U(float(reg)) if which == "U" else step.update_V(float(reg))
-    eng = LinkMUEngine(BitMatrix(X, "cuda:0"), U.shape[1], L.LINK_SIGMOID, L.MODE_PENALTY, lamda=float(link_lamda))
+    if U.shape[1] > L.MAX_KP:   # two 64-column blocks per factor (pybmf_amd/link_wide.py)
+        from ..link_wide import check_wide_link, link_engine
+        check_wide_link(U.shape[1])
+        eng = link_engine(BitMatrix(X, "cuda:0"), U.shape[1], L.LINK_SIGMOID, L.MODE_PENALTY, lamda=float(link_lamda))
+    else:
+        eng = LinkMUEngine(BitMatrix(X, "cuda:0"), U.shape[1], L.LINK_SIGMOID, L.MODE_PENALTY, lamda=float(link_lamda))
     eng.load_factors(U, V)
     eng.prepare()
     import torch

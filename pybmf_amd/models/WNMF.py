@@ -4,7 +4,8 @@ Drop-in for ``PyBMF.models.WNMF`` (``PyBMF/models/WNMF.py``), Frobenius loss.  W
 W='mask' on a matrix whose stored pattern is the whole matrix) a Boolean X runs on the bit kernels (same engine as
 BinaryMFPenalty with the WNMF update rule) and a real-valued X on the fp32-MFMA GEMM; with a proper mask (W='mask' on a
 csr with unstored cells, or a weight matrix) the contractions run over the observed cells (engine.MaskedMUEngine).
-The Kullback-Leibler loss (W='full' or 'mask', Boolean X) runs on the tile-fused link kernels (csrc/link.hip).
+The Kullback-Leibler loss (W='full' or 'mask', Boolean X) runs on the tile-fused link kernels (csrc/link.hip; at a rank
+64 < k <= 128 on csrc/link_wide.hip, pybmf_amd/link_wide.py).
 
 Reference quirk not reproduced: ``WNMF.error`` (:133-144) overwrites exact zeros of X_train and of U V^T with eps in
 place before taking the difference, and the updates that follow see those eps values.  Wherever a row or column has any
@@ -202,6 +203,8 @@ class WNMF(ContinuousModel):
     def _fit_kl(self):
         """beta_loss='kullback-leibler' (WNMF.py:111-129, error :143-145): tile-fused (X / U V^T) V passes, Boolean X."""
         from ..engine import BitMatrix, LinkMUEngine
+        if self.k > L.MAX_KP:   # two 64-column blocks per factor: the link passes over both blocks (pybmf_amd/link_wide.py)
+            return self._fit_kl_wide()
         if not self._boolean:
             # real-valued data (WNMF.py:111-129 on whatever it is given): numerators (W o X / U V^T) F over a list of cells -- every cell
             # under the all-ones mask, the cells with W != 0 under a weight matrix --, denominators = the column sums of the other
@@ -228,6 +231,20 @@ class WNMF(ContinuousModel):
             lo, hi = self._rows
             obs_bits = BitMatrix(pattern, self.device, row_lo=lo, row_hi=hi)
         return self._fit_masked(LinkMUEngine(self._bits, self.k, L.LINK_KL, L.MODE_WNMF, obs_bits=obs_bits, sharded=self._sharded))
+
+    def _fit_kl_wide(self):
+        """The Kullback-Leibler loss at a rank 64 < k <= 128: the same three settings as ``_fit_kl`` (W='full', W='mask' on a pattern,
+        a proper mask / weight matrix) on the two-block engines; Boolean data, one GPU."""
+        from ..engine import BitMatrix
+        from ..link_wide import check_wide_link, link_engine
+        check_wide_link(self.k, sharded=self._sharded, boolean=self._boolean)
+        obs, obs_bits = getattr(self, "_obs", None), None
+        if obs is None and getattr(self, "_mask_is_pattern", False):   # only the objective is restricted to the observed cells
+            from scipy.sparse import csr_matrix
+            Xs = self.X_train.tocsr()
+            pattern = csr_matrix((np.ones(Xs.nnz, dtype=np.uint8), Xs.indices, Xs.indptr), shape=Xs.shape)
+            obs_bits = BitMatrix(pattern, self.device)
+        return self._fit_masked(link_engine(self._bits, self.k, L.LINK_KL, L.MODE_WNMF, obs=obs, obs_bits=obs_bits, with_mae=self.with_mae))
 
     def _note(self, eng):
         """RMSE / MAE of the extra data sets (val / test; train under task='prediction') at the engine's current state."""

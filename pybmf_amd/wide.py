@@ -10,7 +10,9 @@ denominator) -- and what couples the blocks is in csrc/wide.hip: the re-associat
 Python-driven, the interface of ``engine.MaskedMUEngine`` (prepare / update / scalars, and the pipelined iterate / row): a
 correctness row -- no BASELINE configuration has k > 64 -- not a tuned path.  Boolean X, one GPU.  ``WideMUEngine``: the all-ones
 mask (re-associated dense path); ``WideMaskedMUEngine``: W = 'mask' / a weight matrix (contractions over the observed cells,
-``bmf_masked_pass_wide``).  X_val / X_test are scored by ``engine.ObservedScorer`` / ``WholeScorer``, which take the block lists.
+``bmf_masked_pass_wide``; with ``link=`` the link models under a mask, ``bmf_masked_link_pass_wide``).  The link models under the
+all-ones mask are in ``pybmf_amd/link_wide.py``.  X_val / X_test are scored by ``engine.ObservedScorer`` / ``WholeScorer``, which take
+the block lists.
 """
 from __future__ import annotations
 
@@ -245,15 +247,21 @@ class WideMaskedMUEngine:
     the dot product over both blocks and leaves numerators / denominators per block (``bmf_masked_pass_wide``); the fp64 element-wise
     update runs per block (the denominators already carry the coupling).  Whole-matrix scores of a Boolean X (task =
     'reconstruction') from ``bmf_resid_sums_wide`` and ``bmf_cover_count_wide``.  Stepped from Python, one read-back per iteration;
-    one GPU; no link."""
+    one GPU.  ``link`` = L.LINK_SIGMOID (PNLPF) or L.LINK_KL (WNMF, Kullback-Leibler loss): the dot product over both blocks goes through
+    the link inside the pass (``bmf_masked_link_pass_wide``) and the whole-matrix scores are taken against the link prediction
+    (``bmf_link_sums_wide``); under KL the denominator is the column-sum vector of each block of the other factor, as
+    ``engine.MaskedMUEngine`` makes it."""
 
-    def __init__(self, obs, k: int, mode: int, bits: BitMatrix = None, with_mae: bool = True, thr=(0.5, 0.5)):
+    def __init__(self, obs, k: int, mode: int, bits: BitMatrix = None, with_mae: bool = True, thr=(0.5, 0.5), link: int = 0, lamda: float = 10.0):
         if not (BK < k <= MAX_K_WIDE):
             raise NotImplementedError(f"k={k}: the two-block engine takes {BK} < k <= {MAX_K_WIDE}")
         if mode not in (L.MODE_PENALTY, L.MODE_WNMF):
             raise ValueError("mode must be MODE_PENALTY or MODE_WNMF")
+        if link not in (0, L.LINK_SIGMOID, L.LINK_KL) or (link and bits is None):
+            raise NotImplementedError("the two-block masked engine takes link = 0, LINK_SIGMOID or LINK_KL; a link needs the Boolean (0/1) X")
         from .engine import round_up
         self.obs, self.k, self.mode, self.bits, self.with_mae, self.thr = obs, int(k), int(mode), bits, bool(with_mae), thr
+        self.link, self.lamda = int(link), float(lamda)
         self.nb, self.kp = 2, BK
         self.kb = [BK, self.k - BK]
         dev = self.device = obs.device
@@ -271,7 +279,7 @@ class WideMaskedMUEngine:
         self.ubits, self.vbits = [z((mp,), torch.int64) for _ in range(2)], [z((np_,), torch.int64) for _ in range(2)]
         self.ucolbits = [z((BK, mp // 32), torch.int32) for _ in range(2)]
         self.vcolbits = [z((BK, np_ // 32), torch.int32) for _ in range(2)]
-        self.sums, self.sums2 = z((4,), torch.float64), z((2,), torch.float64)
+        self.sums, self.sums2 = z((4,), torch.float64), z((4,), torch.float64)
         self.counts = z((2,), torch.int64)
         self._scal = z((8,), torch.float64)
         self._mae_ws = None
@@ -299,6 +307,16 @@ class WideMaskedMUEngine:
         if ls.get("part_wide") is None:
             ls["part_wide"] = [torch.zeros((max(ls["nseg"], 1), 2, BK), dtype=torch.float32, device=self.device) for _ in range(2)]
         p0, p1 = ls["part_wide"]
+        if self.link:
+            check(lib.bmf_masked_link_pass_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), ptr(ls["wgt"]), rows, ptr(ls["seg_row"]), ptr(ls["seg_beg"]),
+                                                ls["nseg"], ptr(ls["row_seg_ptr"]), ptr(Fself[0]), ptr(Fself[1]), ptr(Fother[0]), ptr(Fother[1]), ptr(p0),
+                                                ptr(p1), ptr(num[0]), ptr(num[1]), ptr(den[0]), ptr(den[1]), ptr(sums), self.link, self.lamda, _stream()),
+                  "bmf_masked_link_pass_wide")
+            if self.link == L.LINK_KL:   # denominator O F_other: the column sums of the other factor (fp64 master), the same for every row
+                F64 = self.V64 if Fother is self.V else self.U64
+                for b in range(2):
+                    den[b].copy_(F64[b].sum(0).float().unsqueeze(0).expand_as(den[b]))
+            return
         check(lib.bmf_masked_pass_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), ptr(ls["wgt"]), rows, ptr(ls["seg_row"]), ptr(ls["seg_beg"]),
                                        ls["nseg"], ptr(ls["row_seg_ptr"]), ptr(Fself[0]), ptr(Fself[1]), ptr(Fother[0]), ptr(Fother[1]), ptr(p0), ptr(p1),
                                        ptr(num[0]), ptr(num[1]), ptr(den[0]), ptr(den[1]), ptr(sums), _stream()), "bmf_masked_pass_wide")
@@ -353,12 +371,16 @@ class WideMaskedMUEngine:
                     self._mae_ws = torch.zeros(((B.m_pad + B.n_pad) * 2 * BK,), dtype=torch.int16, device=self.device)
                     self._tiled_t = B.tiled()[1]
                 self.sums2.zero_()
-                check(lib.bmf_resid_sums_wide(ptr(self._tiled_t), B.ldxt, B.m_pad, B.n_pad, ptr(self.U[0]), ptr(self.U[1]), ptr(self.V[0]), ptr(self.V[1]),
-                                              ptr(self._mae_ws), ptr(self.sums2), 1, st), "bmf_resid_sums_wide")
+                if self.link:   # whole-matrix RMSE / MAE against the link prediction (PNLPF.get_prediction, PNLPF.py:50-58)
+                    check(lib.bmf_link_sums_wide(ptr(B.bits), B.m_pad, B.ldx, self.m, self.n, ptr(self.U[0]), ptr(self.U[1]), ptr(self.V[0]), ptr(self.V[1]),
+                                                 B.n_pad, self.k, self.link, self.lamda, None, ptr(self.sums2), st), "bmf_link_sums_wide")
+                else:
+                    check(lib.bmf_resid_sums_wide(ptr(self._tiled_t), B.ldxt, B.m_pad, B.n_pad, ptr(self.U[0]), ptr(self.U[1]), ptr(self.V[0]), ptr(self.V[1]),
+                                                  ptr(self._mae_ws), ptr(self.sums2), 1, st), "bmf_resid_sums_wide")
                 self.counts.zero_()
                 check(lib.bmf_cover_count_wide(ptr(B.bits), B.m_pad, B.ldx, B.n_pad // 32, ptr(self.ubits[0]), ptr(self.ubits[1]), ptr(self.vcolbits[0]),
                                                ptr(self.vcolbits[1]), B.n_pad // 32, ptr(self.counts), st), "bmf_cover_count_wide")
-                out[3:5] = self.sums2
+                out[3:5] = self.sums2[:2]
                 out[5:7] = self.counts.double()
             h = out.cpu().numpy()
         rec = 0.5 * float(h[0])
