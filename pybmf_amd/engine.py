@@ -1018,21 +1018,14 @@ class ObservedScorer:
             return float("nan"), float("nan")
         ls = self.obs.csr
         if isinstance(U, (list, tuple)):   # 64 < k <= 128: two blocks of 64 columns per factor (pybmf_amd/wide.py)
+            from .blocks import masked_pass_wide
             with torch.cuda.device(self.device):
                 if "wide" not in self._scratch:
-                    z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)  # noqa: E731
-                    self._scratch["wide"] = [z(self.m, 64) for _ in range(4)] + [z(max(ls["nseg"], 1), 2, 64) for _ in range(2)]
-                n0, n1, d0, d1, p0, p1 = self._scratch["wide"]
+                    self._scratch["wide"] = [torch.zeros((self.m, 64), dtype=torch.float32, device=self.device) for _ in range(4)]
+                n0, n1, d0, d1 = self._scratch["wide"]
                 self.sums.zero_()
-                if link:   # the sums of the pass are taken against the link prediction (bmf_masked_link_pass_wide)
-                    check(lib.bmf_masked_link_pass_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), None, self.m, ptr(ls["seg_row"]),
-                                                        ptr(ls["seg_beg"]), ls["nseg"], ptr(ls["row_seg_ptr"]), ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]),
-                                                        ptr(p0), ptr(p1), ptr(n0), ptr(n1), ptr(d0), ptr(d1), ptr(self.sums), int(link), float(lamda),
-                                                        _stream()), "bmf_masked_link_pass_wide")
-                else:
-                    check(lib.bmf_masked_pass_wide(ptr(ls["ptr"]), ptr(ls["idx"]), ptr(ls["val"]), None, self.m, ptr(ls["seg_row"]), ptr(ls["seg_beg"]),
-                                                   ls["nseg"], ptr(ls["row_seg_ptr"]), ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]), ptr(p0), ptr(p1),
-                                                   ptr(n0), ptr(n1), ptr(d0), ptr(d1), ptr(self.sums), _stream()), "bmf_masked_pass_wide")
+                # (the stored entries carry no weights; with `link` the sums of the pass are taken against the link prediction)
+                masked_pass_wide(ls, self.m, U, V, (n0, n1), (d0, d1), self.sums, link, lamda)
                 s = self.sums.cpu().numpy()
             return float(np.sqrt(s[0] / self.nnz)), float(s[1] / self.nnz)
         with torch.cuda.device(self.device):
@@ -1095,21 +1088,20 @@ class WholeScorer:
         if isinstance(U, (list, tuple)):   # 64 < k <= 128: the residual sums with the product over both blocks (bmf_resid_sums_wide)
             if self.bits is None:
                 raise NotImplementedError("a rank above 64 scores Boolean (0/1) data sets only")
+            from .blocks import link_sums_wide, resid_sums_wide, resid_workspace
             B = self.bits
             if link:   # against the link prediction over both blocks (every one of the 128 columns: the padding is zero)
                 with torch.cuda.device(self.device):
                     self.sums.zero_()
-                    check(lib.bmf_link_sums_wide(ptr(B.bits), B.m_pad, B.ldx, self.m, self.n, ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]), B.n_pad, 128,
-                                                 int(link), float(lamda), None, ptr(self.sums), _stream()), "bmf_link_sums_wide")
+                    link_sums_wide(B, self.m, self.n, U, V, 128, link, lamda, None, self.sums)
                     s = self.sums.cpu().numpy()
                 return float(np.sqrt(s[1] / cells)), float(s[0] / cells)
             with torch.cuda.device(self.device):
                 if getattr(self, "_wide_ws", None) is None:
-                    self._wide_ws = torch.zeros(((B.m_pad + B.n_pad) * 2 * 64,), dtype=torch.int16, device=self.device)
+                    self._wide_ws = resid_workspace(B)
                     self._tiled_t = B.tiled()[1]
                 self.sums.zero_()
-                check(lib.bmf_resid_sums_wide(ptr(self._tiled_t), B.ldxt, B.m_pad, B.n_pad, ptr(U[0]), ptr(U[1]), ptr(V[0]), ptr(V[1]),
-                                              ptr(self._wide_ws), ptr(self.sums), 1, _stream()), "bmf_resid_sums_wide")
+                resid_sums_wide(B, self._tiled_t, U, V, self._wide_ws, self.sums)
                 s = self.sums.cpu().numpy()
             return float(np.sqrt(s[1] / cells)), float(s[0] / cells)
         with torch.cuda.device(self.device):
@@ -1141,8 +1133,8 @@ class WholeScorer:
         with torch.cuda.device(self.device):
             self.counts.zero_()
             if isinstance(ubits, (list, tuple)):   # 64 < k <= 128
-                check(lib.bmf_cover_count_wide(ptr(B.bits), B.m_pad, B.ldx, B.n_pad // 32, ptr(ubits[0]), ptr(ubits[1]), ptr(vcolbits[0]),
-                                               ptr(vcolbits[1]), B.n_pad // 32, ptr(self.counts), _stream()), "bmf_cover_count_wide")
+                from .blocks import cover_count_wide
+                cover_count_wide(B, ubits, vcolbits, self.counts)
             else:
                 check(lib.bmf_cover_count(ptr(B.bits), B.m_pad, B.ldx, B.n_pad // 32, ptr(ubits), ptr(vcolbits), B.n_pad // 32, kp,
                                           ptr(self.counts), None, _stream()), "bmf_cover_count")

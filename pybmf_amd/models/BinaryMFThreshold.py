@@ -100,16 +100,14 @@ class BinaryMFThreshold(ContinuousModel):
         from .. import _lib as L
         return self.k > L.MAX_KP
 
-    def _check_wide_rank(self, X_train=None):
+    def _check_wide_rank(self, X_train=None, sharded=False):
         """What a rank above 64 does not take, refused before anything is uploaded: k > 128 and data that is not 0 / 1 (the cell-list
         objective of real-valued data is built for k <= 64 only)."""
         if not self._wide():
             return
-        from ..wide import MAX_K_WIDE
-        if self.k > MAX_K_WIDE:
-            raise NotImplementedError(f"k={self.k}: this build supports k <= {MAX_K_WIDE}")
-        if not (self._boolean if X_train is None else self._values_are_boolean(X_train)):   # (X_train None: after the upload, which decides)
-            raise NotImplementedError(f"k={self.k}: BinaryMFThreshold at a rank above 64 takes Boolean (0/1) data; real-valued data needs k <= 64")
+        from ..blocks import check_wide
+        boolean = self._boolean if X_train is None else self._values_are_boolean(X_train)   # (X_train None: after the upload, which decides)
+        check_wide(self.k, sharded=sharded, boolean=boolean, what="threshold")
 
     # ---- device side ------------------------------------------------------------------------------------------
     def _upload_factors(self):
@@ -117,9 +115,7 @@ class BinaryMFThreshold(ContinuousModel):
         B = self._bits
         wide = self._wide()
         if wide:
-            self._check_wide_rank()
-            if getattr(self, "_sharded", False) or getattr(self, "_rows", (0, self.m)) != (0, self.m):
-                raise NotImplementedError(f"k={self.k}: a rank above 64 runs on one GPU (a sharded run needs k <= 64)")
+            self._check_wide_rank(sharded=getattr(self, "_sharded", False) or getattr(self, "_rows", (0, self.m)) != (0, self.m))
         self._kp = 128 if wide else (32 if self.k <= 32 else 64)
         dev = B.device
         # fp64 on the device: the line search compares F values that differ by min_diff = 1e-3 on F ~ 1e4 (csrc/thresh64.hip)

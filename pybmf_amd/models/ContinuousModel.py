@@ -528,11 +528,9 @@ class ContinuousModel(BaseModel):
         """The two-block engines for a rank 64 < k <= 128 (pybmf_amd/wide.py): one GPU, Boolean data; the all-ones mask on the
         re-associated dense path, W = 'mask' / a weight matrix on the cell lists.  X_val / X_test are scored like at k <= 64 (the scorers
         take the block lists)."""
-        from ..wide import MAX_K_WIDE, WideMaskedMUEngine, WideMUEngine
-        if self.k > MAX_K_WIDE:
-            raise NotImplementedError(f"k={self.k}: this build supports k <= {MAX_K_WIDE}")
-        if self._sharded or not self._boolean:
-            raise NotImplementedError(f"k={self.k}: a rank above {L.MAX_KP} runs on one GPU, on Boolean (0/1) data")
+        from ..blocks import check_wide
+        from ..wide import WideMaskedMUEngine, WideMUEngine
+        check_wide(self.k, sharded=self._sharded, boolean=self._boolean, what="mu")
         if getattr(self, "_obs", None) is not None:
             return WideMaskedMUEngine(self._obs, self.k, mode, bits=self._bits, with_mae=self.with_mae)
         return WideMUEngine(self._bits, self.k, mode, with_mae=self.with_mae)
@@ -543,19 +541,14 @@ class ContinuousModel(BaseModel):
         from ..engine import _stream, round_up
         B = self._bits
         if self.k > L.MAX_KP:   # two 64-column blocks per factor (bmf_resid_sums_wide)
-            from ..wide import BK
+            from ..blocks import BK, resid_sums_wide, resid_workspace, split_into
             lo, hi = getattr(self, "_rows", (0, self.m))
             with torch.cuda.device(B.device):
-                blocks = []
-                for F, rows, rows_pad in ((np.asarray(self.U)[lo:hi], hi - lo, B.m_pad), (np.asarray(self.V), self.n, B.n_pad)):
-                    for c0 in (0, BK):
-                        t = torch.zeros((rows_pad, BK), dtype=torch.float32, device=B.device)
-                        t[:rows, : min(BK, self.k - c0)] = torch.from_numpy(np.ascontiguousarray(F[:, c0:c0 + BK], dtype=np.float32)).to(B.device)
-                        blocks.append(t)
-                ws = torch.zeros(((B.m_pad + B.n_pad) * 2 * BK,), dtype=torch.int16, device=B.device)
+                Ud, Vd = ([torch.empty((rows_pad, BK), dtype=torch.float32, device=B.device) for _ in range(2)] for rows_pad in (B.m_pad, B.n_pad))
+                split_into(Ud, np.asarray(self.U)[lo:hi])
+                split_into(Vd, np.asarray(self.V))
                 sums = torch.zeros(2, dtype=torch.float64, device=B.device)
-                check(lib.bmf_resid_sums_wide(ptr(B.bits_t), B.ldxt, B.m_pad, B.n_pad, ptr(blocks[0]), ptr(blocks[1]), ptr(blocks[2]), ptr(blocks[3]),
-                                              ptr(ws), ptr(sums), 0, _stream()), "bmf_resid_sums_wide")
+                resid_sums_wide(B, B.bits_t, Ud, Vd, resid_workspace(B), sums, tiled=0)
                 s = sums.cpu().numpy()
             s_abs, s_sq = self._sum_over_ranks([s[0], s[1]])
             return s_abs, s_sq

@@ -88,13 +88,15 @@ def _one_step(X, W, U, V, reg, link_lamda, which):
         from ..link_wide import check_wide_link, link_engine
         check_wide_link(U.shape[1])
         eng = link_engine(BitMatrix(X, "cuda:0"), U.shape[1], L.LINK_SIGMOID, L.MODE_PENALTY, lamda=float(link_lamda))
+        one_side = eng.update_side
     else:
         eng = LinkMUEngine(BitMatrix(X, "cuda:0"), U.shape[1], L.LINK_SIGMOID, L.MODE_PENALTY, lamda=float(link_lamda))
+        one_side = eng._side
     eng.load_factors(U, V)
     eng.prepare()
     import torch
     with torch.cuda.device(eng.device):
-        eng._side(which, float(reg))
+        one_side(which, float(reg))
     return eng.factors()[0 if which == "U" else 1]
 
 
