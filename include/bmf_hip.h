@@ -114,6 +114,12 @@ int bmf_make_panel_f16(const float* F, int64_t rows_pad, int64_t ldf, int kp, ui
  * stage) space is cut stream-K fashion into equal slices, one per persistent workgroup (one or two per CU); a row
  * tile therefore receives a shape- and device-dependent number of partial results: bmf_xf_bits_slots() says how many
  * slabs the caller must provide at least (`splits` >= that; surplus slabs are written as zeros).
+ * The per-slab contract.  The (row tile, stage) units -- a row tile = 512 rows, a stage = 128 reduction indices, unit u = tile *
+ * (red_words / 4) + stage, `total` of them -- are cut into equal slices, one per workgroup: with g = min(compute units, total)
+ * every slice is ceil(total / g) units long, the last one clipped by `total`.  Slice s of the launch writes, for every row tile it
+ * meets, its partial sum of the tile (the stages of the tile it holds, all kp columns) into slab slot s - (the slice that holds the
+ * tile's first unit); the slice that holds a tile's last unit zero-fills the slots behind its own up to `splits`.  A slab value is the
+ * fp32 MFMA accumulator of those stages alone, times colscale for an fp16 panel: where the sum is exact in fp32 the slab is exact.
  * rows_pad % 512 == 0, red_words % 4 == 0 (reduction length in 32-bit words), ldw >= red_words, ldw % 4 == 0,
  * ldp >= 32*red_words and ldp % 8 == 0, kp in {32, 64}, terms in {1,2,3}. */
 int bmf_xf_bits_slots(int64_t rows_pad, int64_t red_words, int terms, int kp); /* >= 1, or a negative BMF_ERR_* */

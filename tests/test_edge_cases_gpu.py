@@ -255,10 +255,14 @@ def test_random_shapes_property():
     check()
 
 
-@pytest.mark.parametrize("m,n,k,panel", [(5003, 2999, 37, "f16"), (2999, 5003, 64, "bf16"), (9001, 1031, 5, "f16"), (5003, 2999, 64, "i8"), (1031, 9001, 20, "i8")])
+@pytest.mark.parametrize("m,n,k,panel", [(5003, 2999, 37, "f16"), (2999, 5003, 64, "bf16"), (9001, 1031, 5, "f16"), (5003, 2999, 64, "i8"), (1031, 9001, 20, "i8"),
+                                         (2999, 12901, 37, "f16"), (12901, 2999, 64, "bf16")])
 def test_medium_odd_shapes_many_row_tiles(m, n, k, panel):
-    """Several 512-row tiles with a ragged last one in both orientations, stream-K slices that start and end inside a tile, k
-    that is not a multiple of anything: three updates against the oracle, counts exact."""
+    """Several 512-row tiles with a ragged last one in both orientations, k that is not a multiple of anything: three updates against
+    the oracle, counts exact.  Stream-K slices that start and end inside a tile: on 256 compute units the first three rows give the
+    16-bit kernel at most 240 (tile, stage) units, one stage per slice; only the two 12901 rows (6 x 104 and 26 x 24 = 624 units, three
+    stages per slice, slices that end one tile and start the next in the 6 x 104 orientation) run its multi-stage pipeline.  The int8
+    rows cut their slices in groups of four stages."""
     rs = np.random.RandomState(m + n + k)
     X = (rs.rand(m, n) < 0.25).astype(np.uint8)
     U0 = np.abs(rs.standard_normal((m, k))) * 0.2 + 1e-3
