@@ -251,8 +251,11 @@ def test_xf_f32(env, kp, red_pad):
 @pytest.mark.parametrize("kp,rows_pad,blocks", [(32, 512, 3), (64, 1024, 16), (64, 2560, 7), (64, 128, 64), (64, 130, 5), (32, 20096, 256), (64, 20480, 256),
                                                  (64, 100352, 256), (64, 100352, 1000)])
 def test_gram(env, kp, rows_pad, blocks):
-    """(128 rows on 64 blocks: most waves own no row pair; 130 rows on 5 blocks: partial last groups; the headline shapes: 49 / 10 row pairs
-    per wave through the ring of four load groups.)"""
+    """The SUM of the slabs at the headline shapes (49 / 10 row pairs per wave through the 4-pair loop), against fp64 at 2e-6 of the
+    LARGEST entry, into a zero-filled buffer: a gate that cannot see a wrong small column, a slab at the wrong rows or an idle block
+    that writes nothing.  The slabs themselves -- every entry of every slab bit for bit, NaN-filled buffers, every trip count of both
+    loops, idle waves and blocks, ldf > kp -- are held by tests/test_gram_kernels_gpu.py; this test keeps the large shapes and the
+    pairing with bmf_reduce_slabs."""
     L, E, d = env
     rs = np.random.RandomState(5)
     F = (rs.rand(rows_pad, kp) - 0.25).astype(np.float32)
