@@ -1405,6 +1405,36 @@ int bmf_masked_link_pass_wide(const int64_t* ptr, const int32_t* idx, const floa
                               const float* Fself1, const float* Fother0, const float* Fother1, float* part0, float* part1, float* num0,
                               float* num1, float* den0, float* den1, double* sums, int link, double lamda, void* stream);
 
+/* ---- SimpleThreshold: every (u, v) of a threshold grid in one pass (csrc/thresh_grid.hip) ----------------------------------- */
+
+/* The bits of one fp64 factor block under T threshold vectors: bit (i, c) of panel t is  i < rows && c < k && F64[i][c] > thr[t][c]
+ * (strict, fp64: utils/common.py:110-151 of the reference).  F64: rows_pad x kp, row-major; whatever its padding rows and columns
+ * hold is not read.  thr: T x k.  rowbits ([T][rows_pad], the k-bit word of every row) and colbits ([T][kp][ldcb], bit-column c over
+ * the rows, 32 rows per word) are the layouts bmf_cover_count reads; either may be NULL (not both).  Every row word and the first
+ * rows_pad / 32 words of every bit-column are written, padding included (zeros); nothing else is.  rows_pad % 64 == 0, 1 <= rows <= rows_pad, 1 <= k <= kp, kp in {32, 64}, T >= 1, ldcb >= rows_pad / 32 and
+ * ldcb % 4 == 0; F64 and colbits 16-byte aligned.  A rank 64 < k <= 128 is two blocks and two calls. */
+int bmf_thresh_panels(const double* F64, int64_t rows_pad, int32_t rows, int k, int kp, const double* thr, int T, uint64_t* rowbits,
+                      uint32_t* colbits, int64_t ldcb, void* stream);
+
+/* counts[a][b][0] += TP, counts[a][b][1] += FP of the Boolean product of row-word panel a and bit-column panel b against X, for every
+ * a < A and b < B (counts: uint64 [A][B][2]); integer, exact.  rowbits0: [A][rows_pad]; colbits0: [B][kp][ldcb]; rowbits1 / colbits1:
+ * the second 64-column block of a rank 64 < k <= 128 (both NULL, or both given, and then kp == 64).
+ * PRECONDITION: the row-word panels are nested, panel a + 1 a subset of panel a bit for bit (ascending thresholds give that); the
+ * kernel walks a row from panel A - 1 down and ORs every factor's bit-column once per (row, b).  Panels that are not nested give
+ * counts that mean nothing (bmf_pairs_cover_count takes any).  rows_pad % 64 == 0, words % 4 == 0, ldx >= words, ldx % 4 == 0,
+ * ldcb >= words, ldcb % 4 == 0, kp in {32, 64}, 1 <= A, 1 <= B <= 65535; Xbits, colbits0 / 1 16-byte aligned. */
+int bmf_grid_cover_count(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, int64_t words, const uint64_t* rowbits0,
+                         const uint64_t* rowbits1, int A, const uint32_t* colbits0, const uint32_t* colbits1, int64_t ldcb, int kp, int B,
+                         unsigned long long* counts, void* stream);
+/* counts[t][0] += TP, counts[t][1] += FP for the T pairs (pairs[t][0] = row-word panel, pairs[t][1] = bit-column panel; int32 on the
+ * device; a pair that names a panel outside [0, A) x [0, B) adds nothing).  No nesting is assumed.  Otherwise as above; T >= 1. */
+int bmf_pairs_cover_count(const uint32_t* Xbits, int64_t rows_pad, int64_t ldx, int64_t words, const uint64_t* rowbits0,
+                          const uint64_t* rowbits1, int A, const uint32_t* colbits0, const uint32_t* colbits1, int64_t ldcb, int kp, int B,
+                          const int32_t* pairs, int T, unsigned long long* counts, void* stream);
+/* How the two entry points above cut X at this shape (host arithmetic): chunk_words = words of a bit-column a workgroup holds,
+ * rows_per_block = rows of X per workgroup, a_batch = row-word panels per launch.  `panels` = B, or T for the pair list. */
+int bmf_grid_cover_plan(int64_t rows_pad, int64_t words, int panels, int* chunk_words, int* rows_per_block, int* a_batch);
+
 /* ---- kernel timing (bench.py roofline leg) ----------------------------------------------------------------------- */
 
 /* When enabled, bmf_xf_bits launches made through bmf_penalty_update (and the two sweep launches of bmf_nmf_cd_iterate) are bracketed by hipEvents on `stream`

@@ -344,6 +344,10 @@ SIGNATURES = {
     "bmf_primp_iterate": (C.c_int, [_vp, C.c_int, _f64, _f64, _vp]),
     "bmf_nmf_cd_sweep": (C.c_int, [_vp, _vp, _i64, _i32, C.c_int, C.c_int, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp]),
     "bmf_nmf_cd_iterate": (C.c_int, [C.POINTER(NmfState), C.c_int, _vp]),
+    "bmf_thresh_panels": (C.c_int, [_vp, _i64, _i32, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _i64, _vp]),
+    "bmf_grid_cover_count": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
+    "bmf_pairs_cover_count": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _i64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "bmf_grid_cover_plan": (C.c_int, [_i64, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmf_timer_stride": (C.c_int, [C.c_int]),
     "bmf_timer_enable": (C.c_int, [C.c_int]),
     "bmf_timer_read": (C.c_int, [C.POINTER(C.c_int), C.POINTER(_f64)]),

@@ -18,5 +18,6 @@ from .Panda import Panda
 from .Hyper import Hyper
 from .HyperPlus import HyperPlus
 from .NMFSklearn import NMFSklearn
+from .SimpleThreshold import SimpleThreshold
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus", "NMFSklearn"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus", "NMFSklearn", "SimpleThreshold"]
