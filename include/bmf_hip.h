@@ -771,6 +771,25 @@ int64_t bmf_thresh_trace64_work(int32_t m, int32_t n, int k, int max_pairs);
 int bmf_thresh_trace64(const int32_t* seg_row, const int64_t* seg_beg, const int32_t* seg_len, int32_t nseg, const int32_t* idx, int32_t m, int32_t n, const double* U64, const double* V64, int64_t ldf,
                        int k, const double* uv_host, int32_t n_pairs, double lamda, double sum_x, int want_grad, double* work,
                        double* out_host, double seq, void* stream);
+/* The COLUMNWISE objective of BinaryMFThresholdExColumnwise (csrc/thresh_cols.hip; the module is not in the reference's tree, DESIGN
+ * 9.3 defines it): one threshold per factor column, Us[i][c] = sigmoid(lamda (U[i][c] - us[c])), likewise Vs with vs; F = 1/2 || X -
+ * Us Vs^T ||^2 in trace form and its 2 k gradient components, for a batch of points in one enqueue.  The segment list of the ones,
+ * U64 / V64 / ldf (rows >= m / n and columns >= k are never read), sum_x and the workspace rule (bmf_thresh_cols64_work(m, n, k,
+ * max_points) doubles, device, 16-byte aligned, zero-filled ONCE by the caller) are those of bmf_thresh_trace64.  x: n_points x 2 k
+ * doubles, point after point, each [us_0 .. us_{k-1}, vs_0 .. vs_{k-1}], in memory the DEVICE can read (device or pinned host memory;
+ * it is read once, by the first launch); n_points <= bmf_thresh_cols64_max_points(k) (32 for k <= 16, 16 for k <= 32, 8 above).
+ * out_host: n_points (2 + 2 k) + 1 doubles of PINNED host memory, 16-byte aligned: the record of point p at out[p (2 + 2 k)] is
+ * (seq, 2 F, dF[0 .. 2 k)), dF[c] = d F / d us[c], dF[k + c] = d F / d vs[c] in the sign convention of bmf_thresh_trace64 (with
+ * want_grad = 0 the gradient words are not written); the stamp seq is written behind the values of its record, and out[n_points (2 + 2
+ * k)] = seq last of all, each behind a system-scope fence: a polling host waits for all n_points + 1 stamps.  fp64, every sum in a
+ * fixed order, no floating-point atomics: the same call gives the same bits, and 2 F does not depend on want_grad.  Refused (-1,
+ * bmf_last_error) before anything touches a GPU: null pointers, k outside 1..64, m or n < 1, ldf < k, nseg outside 1..8 m + 64,
+ * n_points outside 1..max_points, misaligned work / out_host. */
+int bmf_thresh_cols64_max_points(int k);
+int64_t bmf_thresh_cols64_work(int32_t m, int32_t n, int k, int max_points);
+int bmf_thresh_cols64(const int32_t* seg_row, const int64_t* seg_beg, const int32_t* seg_len, int32_t nseg, const int32_t* idx, int32_t m,
+                      int32_t n, const double* U64, const double* V64, int64_t ldf, int k, const double* x, int32_t n_points, double lamda,
+                      double sum_x, int want_grad, double* work, double* out_host, double seq, void* stream);
 /* fp64 forms of bmf_thresh_transform / bmf_masked_thresh (the masked objective, W = 'mask' / weights).  partial: 4 *
  * partial_blocks doubles of scratch (one row per workgroup, summed in order); out: 3 doubles (written, not accumulated). */
 int bmf_thresh_transform64(const double* F, int64_t rows_pad, int32_t rows, int k, int kp, double x, double lamda, double* S,

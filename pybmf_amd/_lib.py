@@ -348,6 +348,9 @@ SIGNATURES = {
     "bmf_grid_cover_count": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp]),
     "bmf_pairs_cover_count": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _i64, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
     "bmf_grid_cover_plan": (C.c_int, [_i64, _i64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bmf_thresh_cols64_max_points": (C.c_int, [C.c_int]),
+    "bmf_thresh_cols64_work": (_i64, [_i32, _i32, C.c_int, C.c_int]),
+    "bmf_thresh_cols64": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, C.c_int, _vp, _i32, _f64, _f64, C.c_int, _vp, _vp, _f64, _vp]),
     "bmf_timer_stride": (C.c_int, [C.c_int]),
     "bmf_timer_enable": (C.c_int, [C.c_int]),
     "bmf_timer_read": (C.c_int, [C.POINTER(C.c_int), C.POINTER(_f64)]),

@@ -15,6 +15,7 @@
 // fp64 throughout, block partials added in a fixed order: the same decisions as the reference (golden g4 / g8 / g12; the trace
 // form agrees with the literal one to 3e-15 relative in fp64).
 #include "common.h"
+#include "trace_gram.h"   // sigmoid_pair_t, trace_gram_kernel, kc_of: shared with thresh_cols.hip
 
 #include <cstdlib>
 
@@ -26,12 +27,6 @@ namespace {
 struct TracePairs {
     double u[32], v[32];
 };
-
-__device__ __forceinline__ void sigmoid_pair_t(double z, double lam, double& s, double& d) {   // (as thresh64.hip)
-    if (z >= 0) s = 1.0 / (1.0 + exp(-z));
-    else { const double e = exp(z); s = e / (1.0 + e); }
-    d = lam * s * (1.0 - s);
-}
 
 // S[p][row][c], c < kc: sigmoid-transformed factor of pair p = blockIdx.y (zero for padding rows / columns; one extra all-zero row
 // `rows_alloc - 1` that the cell pass points missing cells at).  Blocks [0, gu) of a pair do U, the rest V.  kc = 1 << kshift.
@@ -139,53 +134,6 @@ __global__ __launch_bounds__(256) void trace_cells_kernel(const int32_t* __restr
     (void)NV;
 }
 
-template <int KC, bool GRAD>
-__global__ __launch_bounds__(256) void trace_gram_kernel(int64_t mrows, int64_t nrows, int npairs_alloc, const double* __restrict__ Us,
-                                                          const double* __restrict__ dUs, const double* __restrict__ Vs, const double* __restrict__ dVs,
-                                                          double* __restrict__ grampart, int uchunks, int vchunks) {
-    constexpr int CR = 4096 / KC;           // rows per chunk
-    __shared__ double sh[2 * CR * KC];      // the S and D chunks (64 KiB)
-    const int gb = (int)blockIdx.x;
-    const int per_pair_blocks = (GRAD ? 2 : 1) * (uchunks + vchunks);
-    const int p = gb / per_pair_blocks;
-    int r = gb % per_pair_blocks;
-    const bool second = r >= uchunks + vchunks;   // the H matrices (S^T D)
-    if (second) r -= uchunks + vchunks;
-    const bool is_u = r < uchunks;
-    const int chunk = is_u ? r : r - uchunks;
-    const int64_t ralloc = is_u ? mrows : nrows;
-    const double* S = (is_u ? Us : Vs) + (int64_t)p * ralloc * KC;
-    const double* D = second ? ((is_u ? dUs : dVs) + (int64_t)p * ralloc * KC) : S;
-    const int64_t r0 = (int64_t)chunk * CR;
-    const int nr = (int)min((int64_t)CR, ralloc - r0);
-    double* sS = sh;
-    double* sD = sh + CR * KC;
-    for (int e = threadIdx.x; e < CR * KC; e += 256) {
-        const bool in = e < nr * KC;
-        sS[e] = in ? S[r0 * KC + e] : 0.0;
-        sD[e] = in ? D[r0 * KC + e] : 0.0;
-    }
-    __syncthreads();
-    constexpr int EPT = KC * KC / 256;   // elements per thread (KC = 16: one)
-    double acc[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) acc[e] = 0.0;
-#pragma unroll 8
-    for (int row = 0; row < CR; ++row) {   // (unrolled: the LDS reads of eight rows in flight; one accumulator, rows in order)
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) {
-            const int el = threadIdx.x + 256 * e;
-            acc[e] = fma(sS[row * KC + el / KC], sD[row * KC + el % KC], acc[e]);
-        }
-    }
-    // grampart[q][p][chunk][KC * KC], q = 0: Us^T Us, 1: Vs^T Vs, 2: Us^T dUs, 3: Vs^T dVs; chunk slots: max(uchunks, vchunks)
-    const int qm = (second ? 2 : 0) + (is_u ? 0 : 1);
-    const int cmax = uchunks > vchunks ? uchunks : vchunks;
-    double* out = grampart + (((int64_t)qm * npairs_alloc + p) * cmax + chunk) * (KC * KC);
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) out[threadIdx.x + 256 * e] = acc[e];
-}
-
 // One block of 1024 threads per pair: the ordered sums, F and dF.  out[4 p + 0..3] = (seq, 2 F, dF_u, dF_v) -- words 1..3 the slots of
 // bmf_thresh_eval64, word 0 the call's sequence number written behind them -- in pinned host memory; the LAST block to finish (a device
 // counter) writes the sequence word out[4 npairs] behind a system-scope fence: the host waits for that word AND for every pair's stamp.  Every sum has a fixed shape: thread-strided partial sums, then a
@@ -279,8 +227,6 @@ __global__ __launch_bounds__(1024) void trace_final_kernel(const double* __restr
         }
     }
 }
-
-int kc_of(int k) { return k <= 16 ? 16 : (k <= 32 ? 32 : 64); }
 
 }  // namespace
 

@@ -172,33 +172,10 @@ class BinaryMFThreshold(ContinuousModel):
         dev = B.device
         with torch.cuda.device(dev):
             # (the list of the ones costs ~16 bytes per one while it is built: a dense or very large X keeps the tile-product objective)
-            if int(B.sum_local) * 16 > min(torch.cuda.mem_get_info(dev)[0] // 4, 4 << 30):
+            from ..ones_list import list_fits, ones_segments
+            if not list_fits(B.sum_local, torch.cuda.mem_get_info(dev)[0]):
                 return
-            shifts = torch.arange(32, dtype=torch.int32, device=dev)
-            step = max(1, (1 << 26) // max(1, B.bits.shape[1] * 32))   # rows per chunk: the unpacked 0 / 1 chunk stays under 256 MB
-            rows_l, cols_l = [], []
-            for a in range(0, self.m, step):
-                b = min(self.m, a + step)
-                cells = ((B.bits[a:b].unsqueeze(-1) >> shifts) & 1).reshape(b - a, -1)[:, : self.n]   # rows a..b of X as 0 / 1
-                rc = torch.nonzero(cells)                                                             # row-major order
-                rows_l.append(rc[:, 0] + a)
-                cols_l.append(rc[:, 1].to(torch.int32))
-                del cells, rc
-            rows_all = torch.cat(rows_l) if rows_l else torch.zeros(0, dtype=torch.int64, device=dev)
-            idx = (torch.cat(cols_l) if cols_l else torch.zeros(0, dtype=torch.int32, device=dev)).contiguous()
-            counts = torch.bincount(rows_all, minlength=self.m)
-            starts = torch.cumsum(counts, 0) - counts
-            # segments of <= 128 cells of one row (a wave's unit of work), the longest first
-            SEG = 128
-            nseg_row = (counts + SEG - 1) // SEG
-            seg_row = torch.repeat_interleave(torch.arange(self.m, device=dev), nseg_row)
-            first = torch.cumsum(nseg_row, 0) - nseg_row
-            within = torch.arange(seg_row.numel(), device=dev) - first[seg_row]
-            seg_beg = starts[seg_row] + within * SEG
-            seg_len = torch.minimum(counts[seg_row] - within * SEG, torch.tensor(SEG, device=dev))
-            o = torch.argsort(seg_len, descending=True, stable=True)
-            seg_row, seg_beg, seg_len = seg_row[o].to(torch.int32).contiguous(), seg_beg[o].contiguous(), seg_len[o].to(torch.int32).contiguous()
-            nseg = int(seg_row.numel())
+            seg_row, seg_beg, seg_len, nseg, idx = ones_segments(B, self.m, self.n)   # segments of <= 128 cells of one row, the longest first
             if idx.numel() == 0 or nseg == 0 or nseg > 8 * self.m + 64:
                 return
             trace_max_pairs, trace_work = ((lib.bmf_thresh_trace_wide_max_pairs, lib.bmf_thresh_trace_wide_work) if self._wide() else
@@ -402,6 +379,9 @@ class BinaryMFThreshold(ContinuousModel):
             self._flush_logs()
             self._log_buffer = None
 
+    def _print_step(self, xk, x_last, alpha, pk):
+        """Further verbose lines of an outer iteration (none here; the columnwise model prints its threshold vectors)."""
+
     def _search(self):
         n_iter = 0
         x_last = self.threshold_to_x()
@@ -436,6 +416,7 @@ class BinaryMFThreshold(ContinuousModel):
             self.print_msg("    num of function evals        : {}".format(fc))
             self.print_msg("    num of gradient evals        : {}".format(gc))
             self.print_msg("    function value update        : {:.3f} -> {:.3f}".format(old_fval, new_fval))
+            self._print_step(xk, x_last, alpha, pk)
             self.x_to_threshold(x_last)
             self.evaluate_with_threshold(n_iter, new_fval)
             improving = self.early_stop(n_iter=n_iter, diff=diff)

@@ -19,5 +19,6 @@ from .Hyper import Hyper
 from .HyperPlus import HyperPlus
 from .NMFSklearn import NMFSklearn
 from .SimpleThreshold import SimpleThreshold
+from .BinaryMFThresholdExColumnwise import BinaryMFThresholdExColumnwise
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus", "NMFSklearn", "SimpleThreshold"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus", "NMFSklearn", "SimpleThreshold", "BinaryMFThresholdExColumnwise"]
