@@ -790,6 +790,30 @@ int64_t bmf_thresh_cols64_work(int32_t m, int32_t n, int k, int max_points);
 int bmf_thresh_cols64(const int32_t* seg_row, const int64_t* seg_beg, const int32_t* seg_len, int32_t nseg, const int32_t* idx, int32_t m,
                       int32_t n, const double* U64, const double* V64, int64_t ldf, int k, const double* x, int32_t n_points, double lamda,
                       double sum_x, int want_grad, double* work, double* out_host, double seq, void* stream);
+/* Max-sum message passing of the MessagePassing model (csrc/mp.hip; the algorithm's module is not in the reference's tree, DESIGN 9.4
+ * defines it).  State, all fp64, device: the hats Phi / Psi, k planes of m x ldn doubles each (ldn = n rounded up to 64; plane f
+ * begins at f m ldn), exactly 0 outside the observed cells and in the padding columns; the marginals Xi [m][k] and Ups [k][ldn]
+ * (columns >= n are never written).  Xbits / Wbits: the bits of X and of the observation pattern, rows of ldx 32-bit words with
+ * 32 ldx >= ldn, at least m rows (engine.BitMatrix); Wbits = NULL observes every cell.  work: bmf_mp_work(m, n, k) doubles.
+ *   bmf_mp_start   hat `which` (0: Phi, 1: Psi) of the observed cell (i, j), factor f := init_scale (2 u - 1), u = the top 53 bits of
+ *                  splitmix64(splitmix64(seed) + ((which m + i) n + j) k + f) over 2^53 (uint64 arithmetic); 0 elsewhere
+ *   bmf_mp_reduce  Xi = cx + the row sums of Phi, Ups = cy + the column sums of Psi: per-tile partials (64 columns; 32 rows) added in
+ *                  ascending tile order, the prior last; d[0] = the largest |new - old| over both marginals (old = what Xi / Ups held);
+ *                  with ubits (m words) and vbits (n words): bit f of word i = Xi[i][f] > 0, of word j = Ups[f][j] > 0
+ *   bmf_mp_step    one Jacobi iteration of every observed cell from the Xi, Ups and hats as they stand (the update of DESIGN 9.4, co1
+ *                  / co0 = the channel constant where X = 1 / 0, damping lr as (1 - lr) old + lr new without FMA), the hats
+ *                  rewritten in place, then the sums, d and the decisions as bmf_mp_reduce forms them
+ * k <= 8 and k <= 16 keep a cell's hats in registers (each plane read once), larger k reads the planes twice.  Fixed-order sums, no
+ * floating-point atomics: the same call gives the same bits.  Refused (-1, bmf_last_error) before anything touches a GPU: null
+ * pointers, k outside 1..64, m or n < 1, ldn that is not n rounded up to 64, ldx that does not cover ldn, one of ubits / vbits alone. */
+int64_t bmf_mp_work(int32_t m, int32_t n, int k);
+int bmf_mp_start(const uint32_t* Wbits, int64_t ldx, int32_t m, int32_t n, int k, int64_t ldn, uint64_t seed, double init_scale,
+                 double* Phi, double* Psi, void* stream);
+int bmf_mp_reduce(const double* Phi, const double* Psi, int32_t m, int32_t n, int k, int64_t ldn, double cx, double cy, double* work,
+                  double* Xi, double* Ups, double* d, uint64_t* ubits, uint64_t* vbits, void* stream);
+int bmf_mp_step(const uint32_t* Xbits, const uint32_t* Wbits, int64_t ldx, int32_t m, int32_t n, int k, int64_t ldn, double co1,
+                double co0, double lr, double cx, double cy, double* Phi, double* Psi, double* work, double* Xi, double* Ups, double* d,
+                uint64_t* ubits, uint64_t* vbits, void* stream);
 /* fp64 forms of bmf_thresh_transform / bmf_masked_thresh (the masked objective, W = 'mask' / weights).  partial: 4 *
  * partial_blocks doubles of scratch (one row per workgroup, summed in order); out: 3 doubles (written, not accumulated). */
 int bmf_thresh_transform64(const double* F, int64_t rows_pad, int32_t rows, int k, int kp, double x, double lamda, double* S,

@@ -351,6 +351,10 @@ SIGNATURES = {
     "bmf_thresh_cols64_max_points": (C.c_int, [C.c_int]),
     "bmf_thresh_cols64_work": (_i64, [_i32, _i32, C.c_int, C.c_int]),
     "bmf_thresh_cols64": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, C.c_int, _vp, _i32, _f64, _f64, C.c_int, _vp, _vp, _f64, _vp]),
+    "bmf_mp_work": (_i64, [_i32, _i32, C.c_int]),
+    "bmf_mp_start": (C.c_int, [_vp, _i64, _i32, _i32, C.c_int, _i64, C.c_uint64, _f64, _vp, _vp, _vp]),
+    "bmf_mp_reduce": (C.c_int, [_vp, _vp, _i32, _i32, C.c_int, _i64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bmf_mp_step": (C.c_int, [_vp, _vp, _i64, _i32, _i32, C.c_int, _i64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bmf_timer_stride": (C.c_int, [C.c_int]),
     "bmf_timer_enable": (C.c_int, [C.c_int]),
     "bmf_timer_read": (C.c_int, [C.POINTER(C.c_int), C.POINTER(_f64)]),

@@ -20,5 +20,6 @@ from .HyperPlus import HyperPlus
 from .NMFSklearn import NMFSklearn
 from .SimpleThreshold import SimpleThreshold
 from .BinaryMFThresholdExColumnwise import BinaryMFThresholdExColumnwise
+from .MessagePassing import MessagePassing
 
-__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus", "NMFSklearn", "SimpleThreshold", "BinaryMFThresholdExColumnwise"]
+__all__ = ["BaseModel", "ContinuousModel", "BinaryMFPenalty", "PNLPF", "WNMF", "BinaryMFThreshold", "ELBMF", "PRIMP", "FastStep", "BooleanModel", "GreConD", "GreConDPlus", "Asso", "AssoIter", "AssoOpt", "MEBF", "Panda", "Hyper", "HyperPlus", "NMFSklearn", "SimpleThreshold", "BinaryMFThresholdExColumnwise", "MessagePassing"]
